@@ -10,7 +10,19 @@ torch.distributed.run) the board is 65536 wide and 65536*N tall, split into N ro
 k-row RCCL halo exchange over xGMI (weak scaling: per-GPU work fixed).  --size/--height select
 other boards (e.g. --size 262144 for configs[3], strong scaling).
 
-Prints ONE JSON line on rank 0 (keys per the driver contract), plus:
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline figure needs:
+set-up, the pre-heat (below), W untimed and N timed generations, the --dump-outputs files if asked
+for, and the JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, the pre-heat's
+cold_start pass, the alive count after the timed steps, and a roofline from the timed region's wall
+time).  Every other measurement and every comparison with the oracle's goldens runs only with
+--full (the legs below; the --no-* options then skip single legs); their keys are null in a plain
+run's line.
+
+--dump-outputs DIR writes what the timed steps computed, the board after their last generation,
+as float .npy files (dump_outputs below): the same arguments give the same board from run to run
+(the board is generated on the device from --seed), so two builds can be compared file by file.
+
+Prints ONE JSON line on rank 0 (keys per the driver contract), plus, with --full:
   roofline     : the bound of the timed kernel.  k >= 2 (temporal blocking, VALU-bound):
                  algorithmic wave64 VALU instructions (12 per 32-cell word per generation) per
                  launch / the launch's average duration from HIP events on the engine's compute
@@ -246,6 +258,14 @@ def parse():
     ap.add_argument("--k", type=int, default=16, help="generations per stencil launch")
     ap.add_argument("--band-rows", type=int, default=0)
     ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the parity check against the "
+                         "oracle's goldens (count and board digest), the instrumented roofline pass, the "
+                         "k sweep, the 262144^2, flips, configs and host-contract legs and the CPU "
+                         "baseline (each --no-* option below skips one of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the board they computed to DIR as float .npy "
+                         "files (see dump_outputs)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-sweep", action="store_true", help="skip the k sweep")
     ap.add_argument("--cpu-size", type=int, default=65536, help="CPU baseline board (the bench board)")
@@ -595,6 +615,48 @@ def board_digest(words, world: int) -> str | None:
     if any(p is None for p in parts):
         return None
     return hashlib.sha256(b"".join(c for p in parts for c in p)).hexdigest()
+
+
+DUMP_ROWS = 128  # rows of the strip --dump-outputs writes cell by cell (at most 32 MiB of float32)
+
+
+def dump_outputs(out_dir: Path, words, cells, alive: int, rank: int, world: int) -> None:
+    """--dump-outputs: this rank's strip after the last timed generation -- what a caller of
+    golhip_step then reads back with golhip_store_words / golhip_store_bytes / golhip_alive_count --
+    as DIR/<name>.npy (at N > 1 each rank writes <name>_rank<r>.npy):
+      row_alive   float64 [rows]         alive cells of every row of the strip (covers every cell);
+      sample_rows float64 [n]            the rows written in full: the first, the last and a fixed
+                                         seeded choice of the others (n <= DUMP_ROWS), ascending;
+      board_rows  float32 [n, width]     those rows, 1.0 = alive, 0.0 = dead;
+      alive_count float64 [1]            golhip_alive_count of the whole board.
+    `words` are the strip's packed uint64 rows (bit x % 64 of word x / 64 is cell x), or None for
+    a width that is no multiple of 64: then `cells` is the strip as bytes (255 = alive)."""
+    import numpy as np
+
+    rows = words.shape[0] if words is not None else cells.shape[0]
+    width = words.shape[1] * 64 if words is not None else cells.shape[1]
+    n = max(1, min(rows, DUMP_ROWS, (32 << 20) // (4 * width)))
+    pick = {0, rows - 1}
+    if n > len(pick):
+        inner = np.random.default_rng(0).permutation(np.arange(1, max(rows - 1, 1)))
+        pick |= {int(y) for y in inner[:n - len(pick)]}
+    pick = np.array(sorted(pick), dtype=np.int64)
+    if words is not None:
+        w8 = np.ascontiguousarray(words, dtype="<u8").view(np.uint8)  # [rows, width / 8]
+        popcount = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1).astype(np.uint8)
+        row_alive = np.concatenate([popcount[w8[y:y + 4096]].sum(axis=1, dtype=np.int64)
+                                    for y in range(0, rows, 4096)])
+        board_rows = np.unpackbits(w8[pick], axis=1, bitorder="little").astype(np.float32)
+    else:
+        row_alive = (cells != 0).sum(axis=1, dtype=np.int64)
+        board_rows = (cells[pick] != 0).astype(np.float32)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    for name, arr in (("row_alive", row_alive.astype(np.float64)),
+                      ("sample_rows", pick.astype(np.float64)),
+                      ("board_rows", board_rows),
+                      ("alive_count", np.array([alive], dtype=np.float64))):
+        np.save(out_dir / f"{name}{tag}.npy", arr)
 
 
 def golden_digest(width: int, height: int, seed: int, turn: int) -> str | None:
@@ -991,10 +1053,18 @@ def main():
     # the whole board after the timed pass, bit for bit: every rank copies its strip to the host
     # now (outside the timed region) and hashes it in 4096-row chunks after the instrumented pass
     # (a second of host hashing here would let the chip's clock drop before that pass)
-    timed_words = strip_words(eng)
+    timed_words = strip_words(eng) if a.full else None
+    # --dump-outputs: the strip as the timed steps left it (packed rows, or the byte board for a
+    # width store_words cannot pack), written out below, after the instrumented pass
+    dump_words = dump_cells = None
+    if a.dump_outputs and width % 64 == 0:
+        dump_words = timed_words if timed_words is not None else eng.store_words()
+    elif a.dump_outputs:
+        dump_cells = eng.store()
     instrumented = None
-    if a.no_timing:
-        launches = -(-a.steps // a.k)
+    evented = a.full and not a.no_timing  # a second pass with per-launch HIP events
+    if not evented:
+        launches = len(plan) or -(-a.steps // a.k)
         kern_ms, gens = dt * 1e3, a.steps
     else:
         # roofline pass: the same warmup + timed turns from the seed again, with per-launch HIP
@@ -1021,7 +1091,7 @@ def main():
                         "kernel_ms": round(kern_ms, 4), "launches": launches,
                         "note": "the same warmup + timed turns from the seed, with per-launch HIP "
                                 "events (roofline.avg_launch_us); value is the uninstrumented pass"}
-    digest = board_digest(timed_words, world)
+    digest = board_digest(timed_words, world) if a.full else None  # collective at N > 1
     del timed_words
     # N > 1: what each rank's timed region was made of, so a scaling line explains its own
     # efficiency -- the rank's wall time in the timed pass, and in the instrumented pass its
@@ -1031,7 +1101,7 @@ def main():
     if dist.is_initialized():
         mine = {"rank": rank, "y0": int(eng.info.y0), "rows": int(local_rows),
                 "timed_ms": round(timed_rank_s[rank] * 1e3, 4)}
-        if not a.no_timing:
+        if evented:
             mine.update({"instrumented_ms": round(inst_rank_s[rank] * 1e3, 4),
                          "kernel_span_ms": round(kern_ms, 4), "launches": launches,
                          "edge_wait_ms": round(edge_ms, 4), "split_blocks": edge_blocks})
@@ -1063,7 +1133,7 @@ def main():
     issued_all = None
     per_depth = [pmc.get(f"{width}x{eng.info.rows}_k{d}", {}).get("valu_instr_per_launch")
                  for d in depth_count]
-    if depth_count and all(per_depth) and kern_ms > 0 and not a.no_timing:
+    if depth_count and all(per_depth) and kern_ms > 0 and evented:
         issued_all = sum(v * depth_count[d] for v, d in zip(per_depth, depth_count))
     traffic = pmc_entry.get("hbm_bytes_per_launch")
     uniform = len(depth_count) == 1  # every timed launch ran the same depth
@@ -1096,6 +1166,8 @@ def main():
             roof["clock_ghz_pmc"] = pmc_entry["clock_ghz"]
     roof.update({"kernel": kernel_name, "avg_launch_us": round(avg_launch_ms * 1e3, 2),
                  "launches": launches, "gens_per_launch": round(gens_per_launch, 3),
+                 "timed_by": ("per-launch HIP events (instrumented pass)" if evented else
+                              "wall time of the timed region (--full adds the instrumented pass)"),
                  "launch_depths": {str(d): c for d, c in sorted(depth_count.items())}})
     hbm_roof = {"achieved": round(hbm_achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "algorithmic_over_peak": round(hbm_achieved / HBM_PEAK_GBS, 4),
@@ -1105,7 +1177,7 @@ def main():
     # parity: the canary against the oracle's golden count of this board (every registered board:
     # configs[2] at N == 1, the weak-scaling boards 65536 x 65536*N at N = 2, 4, 8)
     parity = None
-    if a.seed in (2, 3, 4):
+    if a.full and a.seed in (2, 3, 4):
         exp = golden_count(width, height, a.seed, a.warmup + a.steps)
         if exp is not None:
             parity = {"turn": a.warmup + a.steps, "alive": int(alive_timed), "golden": exp,
@@ -1113,7 +1185,7 @@ def main():
             if cold is not None:
                 parity["cold_start_ok"] = cold["alive_after"] == exp
                 parity["ok"] = parity["ok"] and parity["cold_start_ok"]
-    exp_digest = golden_digest(width, height, a.seed, a.warmup + a.steps)
+    exp_digest = golden_digest(width, height, a.seed, a.warmup + a.steps) if a.full else None
     if exp_digest is not None:
         parity = parity or {"turn": a.warmup + a.steps, "ok": True}
         parity["digest"] = digest
@@ -1123,7 +1195,7 @@ def main():
 
     sweep = None
     k1_launch_us = None
-    if world == 1 and not a.no_sweep:
+    if a.full and world == 1 and not a.no_sweep:
         sweep = {}
         eng.set_fixed_k(True)  # exactly kk deep per launch
         for kk in (1, 2, 4, 8, 10, 12, 14, 16, 32):
@@ -1144,13 +1216,16 @@ def main():
         eng.set_fixed_k(False)
 
     checksum = eng.alive_count()  # collective
+    if a.dump_outputs:
+        dump_outputs(Path(a.dump_outputs), dump_words, dump_cells, int(alive_timed), rank, world)
+    del dump_words, dump_cells
     eng.close()
     del eng
 
     # configs[3]: the 262144^2 board (seed 4) row-strip sharded over the N ranks (strong scaling
     # of a fixed board; per-GPU rate comparable across N), RCCL halos when N > 1
     strong = None
-    if not a.no_strong:
+    if a.full and not a.no_strong:
         n = a.strong_size
         sid = None
         if world > 1 and not host_comm:  # a fresh RCCL unique id per communicator
@@ -1181,7 +1256,7 @@ def main():
     # flips through golhip_step_flips (device ring + one extraction per call) vs the one-turn
     # path (golhip_step(1) + golhip_flips per turn), wall time per turn incl. the host copy
     flips = None
-    if world == 1 and not a.no_flips:
+    if a.full and world == 1 and not a.no_flips:
         flips = {}
         for n in (512, 5120):
             fe = golhip.Engine(n, n, k=a.k)
@@ -1223,14 +1298,14 @@ def main():
                                  "us_per_turn_step1_then_flips": round(dt1 / 64 * 1e6, 2)}
 
     small = None
-    if world == 1 and not a.no_configs:
+    if a.full and world == 1 and not a.no_configs:
         small = configs_leg()
     host5 = None
-    if world == 1 and not a.no_host:
+    if a.full and world == 1 and not a.no_host:
         host5 = cfg5_host_leg()
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         cpu = cpu_baseline(a.cpu_size, a.cpu_turns, threads_per_server=a.cpu_threads_per_server or None)
 
     if rank == 0:
@@ -1241,6 +1316,7 @@ def main():
             "n_gpus": world,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": bool(a.full),
             "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True,
             "scaling": "weak" if not a.height else "strong",

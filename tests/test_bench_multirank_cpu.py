@@ -34,7 +34,7 @@ def _free_port():
     return p
 
 
-def _worker(rank, world, port, out_dir, extra=()):
+def _worker(rank, world, port, out_dir, extra=("--full",)):
     for p in (str(ROOT), str(ROOT / "oracle"), str(PKG)):
         if p not in sys.path:
             sys.path.insert(0, p)
@@ -126,7 +126,7 @@ def test_bench_plain_launch_cpu(tmp_path, world):
     env.update(PYTHONPATH=os.pathsep.join([str(ROOT / "tests" / "fake_site"), env.get("PYTHONPATH", "")]),
                GOLHIP_TEST_FAKE_ENGINE="1", GOLHIP_TEST_FAKE_LOG_DIR=str(tmp_path), OMP_NUM_THREADS="1")
     shm_before = set(Path("/dev/shm").glob("golhip_bench_*"))
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", str(world), "--steps", "20",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", str(world), "--full", "--steps", "20",
                         "--warmup", "5", "--size", "4096", "--strong-size", "1024", "--strong-steps", "16",
                         "--preheat-ms", "20"],
                        cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
@@ -165,11 +165,51 @@ def test_bench_plain_launch_rank_failure(tmp_path):
 def test_bench_rank_path_cpu_process_group_barrier(tmp_path):
     """--rccl-barrier: the timed region between the process group's barriers (here gloo) even when
     every rank is on this node; the same line otherwise."""
-    mp.start_processes(_worker, args=(2, _free_port(), str(tmp_path), ("--rccl-barrier",)), nprocs=2,
+    mp.start_processes(_worker, args=(2, _free_port(), str(tmp_path), ("--full", "--rccl-barrier")), nprocs=2,
                        join=True, start_method="spawn")
     line = json.loads((tmp_path / "rank0.out").read_text().strip().splitlines()[0])
     assert line["process"]["barrier"] == "gloo", line["process"]
     assert line["parity"]["ok"] and line["parity"]["digest_ok"] is True, line["parity"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path, oracle):
+    """Without --full a run is the headline figure alone: one engine per rank, the cold pass and
+    pre-heat, warmup + the timed steps, one host copy for --dump-outputs and the line; no leg beside
+    it, no comparison with the goldens.  --dump-outputs writes each rank's strip after the last
+    timed generation: every row's alive count, and the sampled rows cell by cell, equal the
+    oracle's board at turn warmup + steps."""
+    import numpy as np
+
+    world, dump = 2, tmp_path / "dump"
+    mp.start_processes(_worker, args=(world, _free_port(), str(tmp_path), ("--dump-outputs", str(dump))),
+                       nprocs=world, join=True, start_method="spawn")
+    line = json.loads((tmp_path / "rank0.out").read_text().strip().splitlines()[0])
+    assert line["full"] is False and line["steps"] == 20 and line["ms_per_step"] > 0 and line["value"] > 0
+    for key in ("parity", "instrumented_pass", "strong_262144", "k_sweep_gcups", "configs", "flips_path",
+                "cfg5_host", "cpu_baseline", "hbm_roofline_k1"):
+        assert line[key] is None, key
+    pre = line["cold_start"]["preheat_turns"]
+    for r in range(world):
+        log = [tuple(e) for e in json.loads((tmp_path / f"rank{r}.log").read_text())]
+        assert [e[0] for e in log].count("create") == 1
+        assert [e for e in log if e[0] in ("step", "init", "store_words")] == [
+            ("init", 3), ("step", 5), ("step", 20), ("step", pre), ("init", 3), ("step", 5), ("step", 20),
+            ("store_words",)], log
+    want = oracle.init_random(4096, 4096 * world, seed=3)
+    oracle.packed_run_words(want, 25)
+    cells = np.unpackbits(want.view(np.uint8), axis=1, bitorder="little")
+    assert sorted(p.name for p in dump.iterdir()) == sorted(
+        f"{n}_rank{r}.npy" for r in range(world) for n in ("row_alive", "sample_rows", "board_rows", "alive_count"))
+    for r in range(world):
+        got = {n: np.load(dump / f"{n}_rank{r}.npy") for n in ("row_alive", "sample_rows", "board_rows", "alive_count")}
+        assert got["row_alive"].dtype == np.float64 and got["board_rows"].dtype == np.float32
+        strip = cells[4096 * r:4096 * (r + 1)]
+        assert np.array_equal(got["row_alive"], strip.sum(axis=1))
+        rows = got["sample_rows"].astype(np.int64)
+        assert rows[0] == 0 and rows[-1] == 4095 and len(set(rows)) == len(rows) == 128
+        assert np.array_equal(got["board_rows"], strip[rows])
+        assert got["alive_count"].tolist() == [line["alive_after_timed"]] == [int(cells.sum())]
+    assert sum(p.stat().st_size for p in dump.iterdir()) < 64e6
 
 
 def _barrier_worker(rank, world, port, out_dir):

@@ -153,7 +153,7 @@ def test_bench_rank_path_host_transport(tmp_path):
         env = dict(os.environ, GOLHIP_HOST_COMM="1", PYTHONUNBUFFERED="1")
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
-               "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", str(world),
+               "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", str(world), "--full",
                "--size", "8192", "--steps", "40", "--warmup", "5", "--no-strong",
                "--preheat-ms", "20"]
         p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
@@ -180,7 +180,7 @@ def test_bench_rank_path_real_rccl_shared_gpu(tmp_path):
         env.pop("GOLHIP_HOST_COMM", None)
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
-               "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", str(world),
+               "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", str(world), "--full",
                "--size", "8192", "--steps", "20", "--warmup", "5", "--no-strong",
                "--preheat-ms", "20", "--comm-timeout-ms", "60000"]
         p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
@@ -209,7 +209,7 @@ def test_bench_plain_launch_real_rccl_shared_gpu(tmp_path):
     env = dict(os.environ, GOLHIP_RCCL_SHARED_GPU="1", PYTHONUNBUFFERED="1")
     for v in ("GOLHIP_HOST_COMM", "WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(v, None)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--size", "8192", "--steps", "20",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--full", "--size", "8192", "--steps", "20",
            "--warmup", "5", "--no-strong", "--preheat-ms", "20", "--comm-timeout-ms", "60000",
            "--launch-deadline-s", "240"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)
@@ -234,7 +234,7 @@ def test_bench_rank_process_rehearsal_ring_of_one(tmp_path):
     digest (8192 x 16384, seed 3, oracle goldens) must hold."""
     env = dict(os.environ, GOLHIP_RING_SELF="1", PYTHONUNBUFFERED="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(_free_port()))
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--pg-always", "--size", "8192", "--height", "16384",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--pg-always", "--full", "--size", "8192", "--height", "16384",
            "--steps", "20", "--warmup", "5", "--no-cpu", "--no-sweep", "--no-strong", "--no-configs",
            "--no-flips", "--preheat-ms", "20"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
@@ -248,3 +248,37 @@ def test_bench_rank_process_rehearsal_ring_of_one(tmp_path):
     assert line["process"]["gpu_max_hw_queues"] == "8"
     assert line["parity"]["ok"] and line["parity"]["cold_start_ok"], line["parity"]
     assert line["parity"]["digest_ok"] is True, line["parity"]
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_dumps_outputs(tmp_path, oracle):
+    """`bench.py --gpus 1 --steps N --warmup W --dump-outputs DIR` without --full: the headline figure
+    alone (no leg beside it, no comparison with the goldens in the line), and DIR holds the board the
+    timed steps computed: every row's alive count and the sampled rows cell by cell equal the
+    oracle's board at turn W + N.  4096 x 2048 at up to k = 16: several bands, a 16 + 4 plan."""
+    dump = tmp_path / "dump"
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--size", "4096", "--height", "2048",
+           "--steps", "20", "--warmup", "5", "--preheat-ms", "20", "--dump-outputs", str(dump)]
+    p = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, PYTHONUNBUFFERED="1"), capture_output=True,
+                       text=True, timeout=240)
+    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), p.stdout
+    line = json.loads(lines[0])
+    assert line["full"] is False and line["steps"] == 20 and line["dtype"] == "u32"
+    assert line["unit"] == "GCUPS" and line["higher_is_better"] is True
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    for key in ("parity", "instrumented_pass", "strong_262144", "k_sweep_gcups", "configs", "flips_path",
+                "cfg5_host", "cpu_baseline", "hbm_roofline_k1"):
+        assert line[key] is None, key
+    want = oracle.init_random(4096, 2048, seed=3)
+    oracle.packed_run_words(want, 25)
+    cells = np.unpackbits(want.view(np.uint8), axis=1, bitorder="little")
+    got = {f.stem: np.load(f) for f in dump.iterdir()}
+    assert sorted(got) == ["alive_count", "board_rows", "row_alive", "sample_rows"]
+    assert got["row_alive"].dtype == np.float64 and got["board_rows"].dtype == np.float32
+    assert np.array_equal(got["row_alive"], cells.sum(axis=1))
+    rows = got["sample_rows"].astype(np.int64)
+    assert rows[0] == 0 and rows[-1] == 2047 and len(set(rows)) == len(rows) == 128
+    assert np.array_equal(got["board_rows"], cells[rows])
+    assert got["alive_count"].tolist() == [line["alive_after_timed"]] == [int(cells.sum())]
