@@ -117,21 +117,22 @@ static int device_cus(golhip_t h) {
 // slots to leave free for a concurrent launch (the boundary bands of a split board).
 int64_t auto_band(golhip_t h, int64_t rows_total, int K, int64_t reserve_waves, bool counting) {
     if (h->band_rows > 0) return h->band_rows;
-    const int64_t per = chunk_words(K, h->variant, counting);
+    const bool rule = rule_path(h);  // gol_rule: its own occupancy, 62-word chunks at every depth
+    const int64_t per = stream_chunk_words(h, K, counting);
     const int64_t nchunks = (h->wd + per - 1) / per;
     // Fill the chip in whole rounds of resident waves (CUs x resident waves per CU), so every
     // SIMD gets the same number of equal bands.
     const int cus = device_cus(h);
-    int &wpc = h->waves_per_cu[K][h->variant];
-    if (wpc == 0) wpc = stencil_waves_per_cu(K, h->variant);
+    int &wpc = rule ? h->rule_wpc[K][counting ? 1 : 0] : h->waves_per_cu[K][h->variant];
+    if (wpc == 0) wpc = rule ? rule_waves_per_cu(K, h->rule, counting) : stencil_waves_per_cu(K, h->variant);
     // The one-generation kernel (K = 1, production variant) is HBM-bound: it runs best with 2
     // long-streaming waves per SIMD in one round (measured: 2/SIMD 21.9, 4/SIMD 21.1, 1/SIMD
     // 19.6 TCUPS at 65536^2; uneven rounds lose 10-20 %, profiles/r01_tune_step1.txt).
-    const bool step1 = K == 1 && variant_is_production_family(h->variant);
+    const bool step1 = K == 1 && !rule && variant_is_production_family(h->variant);
     const int64_t capacity = (int64_t)cus * (step1 ? kStep1WavesPerCu : wpc);
     constexpr int64_t kMaxBand = 4096;
-    const bool skew = h->variant == kVariantSkew || h->variant == kVariantSkewD2 ||
-                      h->variant == kVariantSkewLdsPf || h->variant == kVariantSkewLdsD2;
+    const bool skew = !rule && (h->variant == kVariantSkew || h->variant == kVariantSkewD2 ||
+                                h->variant == kVariantSkewLdsPf || h->variant == kVariantSkewLdsD2);
     const int64_t lag = skew ? 3 * K - 1 : 2 * K;
     // A wave runs band + lag steps in blocks of 8 (the kernel's prefetch ring); bands are rounded
     // so that full bands end on a block boundary instead of computing up to 7 discarded rows.
@@ -155,11 +156,16 @@ int64_t auto_band(golhip_t h, int64_t rows_total, int K, int64_t reserve_waves, 
         // 103.2 at band 256 (8.2), 106.5 at one round (band 528); at 262144^2 the waves just over
         // a multiple lose 5-10 % the same way.
         const int64_t simds = 4 * (int64_t)cus;  // gfx9: 4 SIMDs per CU
-        const int64_t m0 = std::max<int64_t>(2, 2 * (int64_t)wpc / 4);
+        int64_t m0 = std::max<int64_t>(2, 2 * (int64_t)wpc / 4);
         // The concurrent boundary bands (reserve_waves waves of K rows each) are short: they count
         // by their rows of work, not as whole wave slots (a full slot each pushed the 65536-row
         // interior from 264- to 272-row bands: -2.5 % on the RCCL ring of one).
         const double work = (double)rows_total * (double)nchunks + (double)reserve_waves * K;
+        // gol_rule keeps up to 7 waves per SIMD (the slabs that run small B3/S23 boards are not for
+        // it): where two rounds of residency would cut the bands under 4 K rows -- half of such a
+        // band's steps are its 2 K-row pipeline fill -- plan from one round (16384^2, HighLife at
+        // K = 8: 16-row bands ran 31.0 TCUPS against 43.9 with 24-row bands)
+        if (rule && work / (double)(m0 * simds) < 4.0 * K) m0 = std::max<int64_t>(2, (int64_t)wpc / 4);
         // Among m within 1 % of the least cost take the largest (more, shorter bands measured
         // 3 % faster at 262144^2: band 2232 vs 3728).
         std::vector<std::pair<int64_t, double>> cand;  // (band, cost) per m
@@ -457,7 +463,7 @@ StencilParams make_params(golhip_t h, const Shard &s, int K, int64_t r0b, int64_
     p.lo = -(int64_t)h->halo;
     p.hi = s.rows + h->halo;
     p.wd = h->wd;
-    const int per = chunk_words(K, h->variant, counting);
+    const int per = stream_chunk_words(h, K, counting);
     p.nchunks = (h->wd + per - 1) / per;
     return p;
 }
@@ -510,6 +516,11 @@ int golhip_launch_kind_counts(golhip_t h, int k, int counting, int *kind, int *p
     if (!h || !kind || !param || k < 1 || k > kMaxK) return GOLHIP_ERR_ARG;
     *kind = 0;
     *param = 0;
+    if (rule_path(h)) {  // any rule but B3/S23: gol_rule on every board, strips included
+        *kind = 5;
+        *param = rule_catalogued(h->rule.birth, h->rule.survive) ? 1 : 0;
+        return GOLHIP_OK;
+    }
     if (h->split) return GOLHIP_OK;  // strips: the streaming kernel around the halo exchange
     if (int W = 0, R = 0; board_applies(h, &W, &R)) {  // the whole board in one workgroup
         *kind = 4;

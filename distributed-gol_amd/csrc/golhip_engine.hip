@@ -293,6 +293,11 @@ int step_block(golhip_t h, int K, int64_t slot_gen, int64_t diff_slot = kDiffNon
         if (!h->split) {
             StencilParams p = make_params(h, s, K, 0, s.rows, 0, 0, 0, slots != nullptr);
             p.diff = diff;
+            if (rule_path(h)) {  // any rule but B3/S23: gol_rule, whatever the board's Life kernel is
+                h->act_valid = false;
+                HIPCHK(h, launch_rule(K, h->rule, in, out, p, slots, s.compute));
+                continue;
+            }
             if (hk && hk->launch_params) hk->launch_params(h, s, K, slots != nullptr, p);  // tuning: stamps
             // a K-deep ring launch (ring_depth: a production register slab) writes the flips of
             // each of its K generations into K consecutive ring slots
@@ -319,17 +324,17 @@ int step_block(golhip_t h, int K, int64_t slot_gen, int64_t diff_slot = kDiffNon
             // first by default; edge_first: tuning A/B) only matters when both are ready at once
             if (interior_first) {
                 HIPCHK(h, hipEventRecord(s.ev_ready, s.compute));  // the end of the previous block
-                HIPCHK(h, launch_stencil(K, h->variant, in, out, pi, slots, s.compute));
+                HIPCHK(h, launch_stream(h, K, in, out, pi, slots, s.compute));
                 int rc = exchange_halos(h, K, false);
                 if (rc) return rc;
             } else if (!h->edge_first) {
-                HIPCHK(h, launch_stencil(K, h->variant, in, out, pi, slots, s.compute));
+                HIPCHK(h, launch_stream(h, K, in, out, pi, slots, s.compute));
             }
             HIPCHK(h, hipStreamWaitEvent(s.edge, s.ev_ready, 0));
             HIPCHK(h, hipStreamWaitEvent(s.edge, s.ev_halo, 0));
-            HIPCHK(h, launch_stencil(K, h->variant, in, out, pb, slots, s.edge));
+            HIPCHK(h, launch_stream(h, K, in, out, pb, slots, s.edge));
             HIPCHK(h, hipEventRecord(s.ev_edge, s.edge));
-            if (h->edge_first) HIPCHK(h, launch_stencil(K, h->variant, in, out, pi, slots, s.compute));
+            if (h->edge_first) HIPCHK(h, launch_stream(h, K, in, out, pi, slots, s.compute));
             TimingPair *tp = nullptr;  // timing: the join's wait on the compute stream
             if (h->timing && &s == &h->shards[0]) {
                 int rc = edge_pair(h, &tp);
@@ -345,7 +350,7 @@ int step_block(golhip_t h, int K, int64_t slot_gen, int64_t diff_slot = kDiffNon
             HIPCHK(h, hipStreamWaitEvent(s.compute, s.ev_halo, 0));
             StencilParams p = make_params(h, s, K, 0, s.rows, 0, 0, 0, slots != nullptr);
             p.diff = diff;
-            HIPCHK(h, launch_stencil(K, h->variant, in, out, p, slots, s.compute));
+            HIPCHK(h, launch_stream(h, K, in, out, p, slots, s.compute));
         }
     }
     if (h->timing) {
@@ -397,7 +402,7 @@ int board_block(golhip_t h, int K, int W, int R, int64_t slot_gen, int64_t diff_
 // production slab shape; anything else (strips, the streaming kernel of large boards, the tail)
 // runs one-generation launches, each writing its slot.
 int ring_depth(golhip_t h, int64_t left, bool counting) {
-    if (h->split || h->shards.size() != 1) return 1;
+    if (h->split || h->shards.size() != 1 || rule_path(h)) return 1;  // gol_rule: one slot per launch
     for (int K : {16, 12, 8}) {
         if (K > left || K > h->k) continue;
         const RegKernel rk = pick_reg_kernel(h, h->shards[0].rows, K, counting);
@@ -489,7 +494,11 @@ int run_steps(golhip_t h, int64_t turns, uint64_t *alive_per_turn, bool ring) {
                     h->variant);
     const bool counting = alive_per_turn != nullptr;
     int bw = 0, br = 0;  // the whole-board kernel: W waves x R rows per segment
-    const bool board = !ring && board_applies(h, &bw, &br);
+    // any rule but B3/S23: every launch is gol_rule at the largest of its depths <= min(k, turns
+    // left) -- no whole-board kernel, no graph replay (every rank of a rank-mode board derives the
+    // same sequence: it depends on k and the turn count alone)
+    const bool rule = rule_path(h);
+    const bool board = !ring && !rule && board_applies(h, &bw, &br);
     const int kmax = pick_k(h->k);
     const bool reg = !ring && !h->split && h->shards.size() == 1 &&
                      pick_reg_kernel(h, h->shards[0].rows, kmax, counting).kind != 0;
@@ -498,7 +507,7 @@ int run_steps(golhip_t h, int64_t turns, uint64_t *alive_per_turn, bool ring) {
     // largest strip of the board, so every rank of a rank-mode board plans the same depths.  A
     // register-slab board runs its tuned full depth (reg: fixed; best_rate_k's rates are the
     // streaming kernel's), also without graphs, where only full-depth slabs skip stable slabs
-    LaunchPlanner plan((double)h->L * (double)plan_rows(h), ring ? 1 : h->k, turns, !ring && graph_worthy(h, kmax),
+    LaunchPlanner plan((double)h->L * (double)plan_rows(h), ring ? 1 : h->k, turns, !ring && !rule && graph_worthy(h, kmax),
                        h->fixed_k || ring || reg, h->track_flips, h->count_window, stream, reg && !h->fixed_k);
     if (counting) {
         // pinned host counts for calls that replay no graph (their graph replays would copy each
@@ -553,7 +562,9 @@ int run_steps(golhip_t h, int64_t turns, uint64_t *alive_per_turn, bool ring) {
             if (counting) win += K;
             continue;
         }
-        const int K = ring ? ring_depth(h, turns - done, counting) : plan.next();
+        const int K = ring   ? ring_depth(h, turns - done, counting)
+                      : rule ? rule_pick_k(std::min<int64_t>(h->k, turns - done))
+                             : plan.next();
         if (K == 0) {  // one graph replay of M x Kfull generations
             const int M = plan.last_M;
             if (counting) {  // the graph finalizes its own generations from window slot 0

@@ -182,6 +182,11 @@ struct golhip_engine {
     // kBoardAutoRows rows --, 0 off, 1 every board it fits)
     int board_kernel = -1;
     int64_t act_key[3] = {0, 0, 0};
+    // the rule (golhip_set_rule*): B3/S23 runs the production kernels exactly as planned; any other
+    // rule routes every launch to gol_rule (rule_path), bypassing the register slabs, gol_tile, the
+    // level split, gol_board, graph replays and stable-slab skipping
+    golhip::RuleMasks rule{golhip::kLifeBirth, golhip::kLifeSurvive};
+    int rule_wpc[golhip::kMaxK + 1][2] = {};  // occupancy cache of the rule's kernels per (depth, counting)
     // RCCL fail-fast (rank mode): every host wait on work that can depend on an RCCL transfer polls
     // ncclCommGetAsyncError against a deadline and fails the handle when it passes
     // (golhip_set_comm_timeout); the communicator is non-blocking, so no RCCL call blocks the host
@@ -310,6 +315,22 @@ int create_common(golhip_t h);
 // shard's streams; a stream still busy after it is left to the process's teardown, and its memory
 // is not freed under it.
 void free_shard(Shard &s, int64_t drain_ms = 0, bool comm_failed = false);
+
+// ---- engine_rule.hip: life-like rules ----------------------------------------------------------
+// True when the handle's rule is not B3/S23: every launch runs gol_rule.
+inline bool rule_path(const golhip_engine *h) {
+    return h->rule.birth != kLifeBirth || h->rule.survive != kLifeSurvive;
+}
+// The K-generation launch of a streaming-kernel call site: the production stencil, or gol_rule.
+inline hipError_t launch_stream(golhip_t h, int K, const uint32_t *in, uint32_t *out, const StencilParams &p,
+                                unsigned long long *slots, hipStream_t s) {
+    return rule_path(h) ? launch_rule(K, h->rule, in, out, p, slots, s)
+                        : launch_stencil(K, h->variant, in, out, p, slots, s);
+}
+// Words per column chunk of the handle's streaming launch of depth K.
+inline int stream_chunk_words(const golhip_engine *h, int K, bool counting) {
+    return rule_path(h) ? kRuleChunkWords : chunk_words(K, h->variant, counting);
+}
 
 // ---- engine_plan.hip: the launch planner --------------------------------------------------------
 // Rows per strip the planner ranks depths by: the largest strip, ceil(height / strips) (every rank

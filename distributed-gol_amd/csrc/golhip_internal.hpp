@@ -153,6 +153,48 @@ inline int chunk_words(int K, int variant, bool counting = false) {
 GOLHIP_STENCIL_DEPTHS(GOLHIP_X)
 #undef GOLHIP_X
 
+// ---- life-like rules (gol_rule, golhip_rule.hpp; one translation unit per depth, rule_k<K>.hip) ----
+// Outer-totalistic rules on the Moore neighbourhood as two 9-bit masks: birth bit n = a dead cell
+// with n live neighbours is born, survive bit n = a live cell with n live neighbours stays alive.
+// B3/S23 runs the production kernels above; every other rule runs gol_rule (launch kind 5).
+constexpr uint32_t kRuleMaskBits = 0x1ffu;
+constexpr uint32_t kLifeBirth = 0x008u, kLifeSurvive = 0x00Cu;
+struct RuleMasks {
+    uint32_t birth, survive;
+};
+// Rules with a constant-folded instantiation (RuleConst<B, S>: the rule's truth tables are v_bitop3
+// immediates); every other rule runs the table form (RuleTable: the 18 rule bits are kernel
+// arguments).  One entry per rule: X(birth mask, survive mask).
+#define GOLHIP_RULE_CATALOGUE(X)                    \
+    X(0x048, 0x00C) /* HighLife     B36/S23      */ \
+    X(0x1C8, 0x1D8) /* Day & Night  B3678/S34678 */ \
+    X(0x004, 0x000) /* Seeds        B2/S         */ \
+    X(0x0AA, 0x0AA) /* Replicator   B1357/S1357  */
+inline bool rule_catalogued(uint32_t birth, uint32_t survive) {
+#define GOLHIP_X(B, S) \
+    if (birth == (B) && survive == (S)) return true;
+    GOLHIP_RULE_CATALOGUE(GOLHIP_X)
+#undef GOLHIP_X
+    return false;
+}
+// Launch depths of gol_rule: any turn count decomposes; the rule path runs the largest depth that
+// fits (rule_pick_k).
+#define GOLHIP_RULE_DEPTHS(X) X(1) X(2) X(4) X(8)
+constexpr int kRuleChunkWords = 62;  // lanes 1..62 store whole words (drifting sums, K <= 32)
+inline int rule_pick_k(int64_t n) { return n >= 8 ? 8 : n >= 4 ? 4 : n >= 2 ? 2 : 1; }
+#define GOLHIP_X(K)                                                                            \
+    hipError_t launch_rule_k##K(RuleMasks rm, const uint32_t *in, uint32_t *out,              \
+                                const StencilParams &p, unsigned long long *slots, hipStream_t s); \
+    const void *rule_fn_k##K(RuleMasks rm, bool counting);
+GOLHIP_RULE_DEPTHS(GOLHIP_X)
+#undef GOLHIP_X
+// Launch the K-generation rule stencil (K one of GOLHIP_RULE_DEPTHS), same StencilParams contract
+// as launch_stencil (both ranges, graded bands, wrap / halo rows, prio, slots, diff).
+hipError_t launch_rule(int K, RuleMasks rm, const uint32_t *in_row0, uint32_t *out_row0,
+                       const StencilParams &p, unsigned long long *count_slots, hipStream_t s);
+// Resident waves per CU of this rule's K-deep launch (occupancy query), for sizing the grid.
+int rule_waves_per_cu(int K, RuleMasks rm, bool counting);
+
 // Kernels beyond the production set.  Empty in the production library; the tuning library's
 // TUs (csrc/tuning/) fill it from static initialisers when the library loads.  Every dispatcher
 // asks the production kernels first and falls back to an entry here (a null entry: the kernel is

@@ -300,6 +300,8 @@ int golhip_step_persistent(golhip_t h, int64_t turns, uint64_t *alive_per_turn) 
     constexpr int K = 16;
     if (h->split || h->shards.size() != 1 || h->k < K || h->variant != kVariantProd)
         return fail(h, GOLHIP_ERR_STATE, "golhip_step_persistent: a single-strip board of the production kernels, k >= 16");
+    if (rule_path(h))  // gol_slabq is a B3/S23 kernel
+        return fail(h, GOLHIP_ERR_STATE, "golhip_step_persistent: the handle's rule is not B3/S23 (use golhip_step)");
     if (h->track_flips)  // gol_slabq writes no flips board
         return fail(h, GOLHIP_ERR_STATE, "golhip_step_persistent: flip tracking is on (use golhip_step)");
     Shard &s = h->shards[0];

@@ -53,6 +53,7 @@ EXPORTS = [
     "golhip_step_flips", "golhip_flips_ring_capacity", "golhip_flips_fetch",
     "golhip_step_flips_rows", "golhip_flips_fetch_rows",
     "golhip_checkpoint_save", "golhip_checkpoint_load", "golhip_checkpoint_info",
+    "golhip_parse_rule", "golhip_set_rule", "golhip_set_rule_masks", "golhip_get_rule",
 ]
 
 
@@ -217,6 +218,11 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
         "golhip_activity_stats": ([H, i64p, i64p], i32),
         "golhip_launch_plan": ([i64, i64, i32, i32, i64, ctypes.c_void_p, ctypes.c_size_t,
                                 ctypes.POINTER(ctypes.c_size_t)], i32),
+        "golhip_parse_rule": ([ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32),
+                               ctypes.POINTER(ctypes.c_uint32)], i32),
+        "golhip_set_rule": ([H, ctypes.c_char_p], i32),
+        "golhip_set_rule_masks": ([H, ctypes.c_uint32, ctypes.c_uint32], i32),
+        "golhip_get_rule": ([H, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)], i32),
         "golhip_launch_kind": ([H, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], i32),
         "golhip_launch_kind_counts": ([H, i32, i32, ctypes.POINTER(ctypes.c_int),
                                        ctypes.POINTER(ctypes.c_int)], i32),
@@ -371,6 +377,24 @@ def launch_plan(width: int, height: int, k: int, turns: int, strips: int = 1) ->
     return [int(x) for x in out[: n.value]]
 
 
+def parse_rule(text: str | bytes | None, lib: ctypes.CDLL | None = None) -> tuple[int, int]:
+    """"B36/S23" -> (birth, survive) masks: bit n of birth = a dead cell with n live neighbours is
+    born, bit n of survive = a live cell with n live neighbours stays alive (pure host, no device)."""
+    L = lib if lib is not None else load_library()
+    b, s = ctypes.c_uint32(), ctypes.c_uint32()
+    raw = text.encode() if isinstance(text, str) else text
+    rc = L.golhip_parse_rule(raw, ctypes.byref(b), ctypes.byref(s))
+    if rc != OK:
+        raise GolHipError(rc, L.golhip_last_error(None).decode() or f"bad rule {text!r}")
+    return b.value, s.value
+
+
+def rule_string(birth: int, survive: int) -> str:
+    """The canonical text of a rule's masks: digits ascending, "B36/S23"."""
+    digits = lambda m: "".join(str(n) for n in range(9) if (m >> n) & 1)  # noqa: E731
+    return f"B{digits(birth)}/S{digits(survive)}"
+
+
 def checkpoint_info(path) -> tuple[int, int, int]:
     """(width, height, turn) of a checkpoint file (pure host, no device)."""
     w, h, t = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
@@ -395,7 +419,7 @@ class Engine:
     def __init__(self, width: int, height: int, ngpus: int = 1, k: int = 1, *, rank: int | None = None,
                  world_size: int = 1, device: int = 0, nccl_id: bytes | None = None,
                  strips: int | None = None, host_comm: GlooHostComm | None = None,
-                 lib: ctypes.CDLL | None = None):
+                 lib: ctypes.CDLL | None = None, rule: str | tuple[int, int] | None = None):
         self.last_call = "golhip_create"
         L = _CallLog(lib if lib is not None else load_library(), self)
         self._L = L
@@ -415,6 +439,12 @@ class Engine:
             why = L.golhip_last_error(None).decode() or L.golhip_strerror(rc).decode()
             raise GolHipError(rc, why)
         self.info = self.get_info()
+        if rule is not None:  # default: B3/S23
+            try:
+                self.set_rule(rule)
+            except Exception:
+                self.close()
+                raise
 
     # -- plumbing
     def _check(self, rc: int) -> int:
@@ -468,6 +498,31 @@ class Engine:
         words = np.ascontiguousarray(words, dtype=np.uint64)
         assert words.shape == (self.info.rows, self.info.width // 64)
         self._check(self._L.golhip_load_words(self._h, words.ctypes.data))
+
+    # -- the rule
+    def set_rule(self, rule: str | tuple[int, int]):
+        """golhip_set_rule: "B36/S23" or (birth, survive) masks.  Keeps the board, the turn and every
+        setting; B3/S23 runs the production kernels, any other rule the rule-generic kernel
+        (launch_kind: "rule").  A checkpoint does not hold the rule: set it again after loading."""
+        if isinstance(rule, (str, bytes)):
+            self._check(self._L.golhip_set_rule(self._h, rule.encode() if isinstance(rule, str) else rule))
+        else:
+            birth, survive = rule
+            self._check(self._L.golhip_set_rule_masks(self._h, int(birth), int(survive)))
+
+    def set_rule_masks(self, birth: int, survive: int):
+        self.set_rule((birth, survive))
+
+    @property
+    def rule_masks(self) -> tuple[int, int]:
+        b, s = ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(self._L.golhip_get_rule(self._h, ctypes.byref(b), ctypes.byref(s)))
+        return b.value, s.value
+
+    @property
+    def rule(self) -> str:
+        """The handle's rule in canonical form, e.g. "B36/S23"."""
+        return rule_string(*self.rule_masks)
 
     # -- hot path
     def step(self, turns: int, counts: bool = False) -> np.ndarray | None:
@@ -634,11 +689,12 @@ class Engine:
 
     def launch_kind(self, k: int, counts: bool = False) -> tuple[str, int]:
         """The kernel a k-deep launch runs (with / without per-generation counts): ("stream", 0),
-        ("split", S), ("tile", T), ("slab", [10000 NC +] 100 W + S) or ("board", 100 W + R)."""
+        ("split", S), ("tile", T), ("slab", [10000 NC +] 100 W + S), ("board", 100 W + R) or, for
+        any rule but B3/S23, ("rule", 1 constant-folded / 0 table form)."""
         kind, param = ctypes.c_int(), ctypes.c_int()
         self._check(self._L.golhip_launch_kind_counts(self._h, k, int(counts), ctypes.byref(kind),
                                                       ctypes.byref(param)))
-        return ("stream", "split", "tile", "slab", "board")[kind.value], param.value
+        return ("stream", "split", "tile", "slab", "board", "rule")[kind.value], param.value
 
     def sync(self):
         self._check(self._L.golhip_sync(self._h))

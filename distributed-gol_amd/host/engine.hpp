@@ -47,6 +47,7 @@ public:
         return c;
     }
     void set_k(int k) { check(golhip_set_k(h_, k)); }
+    void set_rule(const std::string &rule) { check(golhip_set_rule(h_, rule.c_str())); }
     uint64_t alive_count() {
         uint64_t v = 0;
         check(golhip_alive_count(h_, &v));

@@ -331,6 +331,7 @@ void run_impl(const Params &p, Channel<Event> *events, Channel<char> *keyPresses
     // paused state -- here the checkpoint file -- and resumes from it when the size matches
     // (broker/broker.go:124-141 clears `paused` either way).
     auto eng = std::make_unique<Engine>(p.ImageWidth, p.ImageHeight, o.ngpus, o.k);
+    eng->set_rule(o.rule);  // a bad rule throws EngineError with the parser's message
     bool resumed = false;
     const std::string ckpt = checkpoint_file(o);
     if (p.Turns > 0 && file_exists(ckpt)) {

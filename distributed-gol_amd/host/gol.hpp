@@ -104,6 +104,10 @@ struct RunOptions {
     // writes it, the next Run with Turns > 0 consumes it (CheckStates) and resumes when the size
     // matches.  Empty: <out_dir>/broker_state.ckpt.
     std::string checkpoint_path;
+    // The rule, "B<digits>/S<digits>" (golhip_set_rule), applied after the engine is created -- also
+    // after a resume: the checkpoint does not record it.  Default: the reference's rule
+    // (server/server.go:21-52).
+    std::string rule = "B3/S23";
 };
 
 // gol/gol.go:14 -- runs the whole simulation, sends events, closes `events` at the end.

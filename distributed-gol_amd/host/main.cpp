@@ -1,7 +1,8 @@
 // main.cpp -- headless CLI mirroring the reference's main.go:13-68 flags on the C++ host.
 //   -t threads  -w width  -h height  -turns N  -noVis (always headless: SDL is out of scope)
 //   extra: -gpus G (row strips), -k K (max generations per launch), -images DIR, -out DIR,
-//          -checkpoint PATH (the 'q' state file; default OUT/broker_state.ckpt), -flips
+//          -checkpoint PATH (the 'q' state file; default OUT/broker_state.ckpt), -flips,
+//          -rule B36/S23 (a life-like rule; default B3/S23; a bad rule exits with status 2)
 // Keys p/s/q/k are read from stdin (one character per line), like the SDL key loop
 // (sdl/loop.go:17-27) would deliver them.
 #include <cstdio>
@@ -11,6 +12,7 @@
 #include <string>
 #include <thread>
 
+#include "../../include/golhip.h"
 #include "gol.hpp"
 
 int main(int argc, char **argv) {
@@ -30,7 +32,12 @@ int main(int argc, char **argv) {
         else if (a == "-out") o.out_dir = next();
         else if (a == "-checkpoint") o.checkpoint_path = next();
         else if (a == "-flips") o.flip_events = true;
+        else if (a == "-rule") o.rule = i + 1 < argc ? argv[++i] : "";
         else if (a == "-noVis") {}
+    }
+    if (uint32_t b = 0, s = 0; golhip_parse_rule(o.rule.c_str(), &b, &s) != GOLHIP_OK) {
+        std::fprintf(stderr, "gol: %s\n", golhip_last_error(nullptr));
+        return 2;
     }
     std::printf("Threads: %d\nWidth: %d\nHeight: %d\n", p.Threads, p.ImageWidth, p.ImageHeight);
     gol::Channel<gol::Event> events(1000);  // main.go:210

@@ -148,12 +148,47 @@ int golhip_load_words(golhip_t h, const uint64_t *in);
  * matches, gol/distributor.go:69-91).  Here that state is a file: the handle's rows as packed
  * bits (64-byte header: "GOLCKPT1", version 1, width, height, y0, rows, turn, row bytes; then
  * rows x ceil(width/8) bytes, LSB-first) and the completed turn, written atomically (tmp +
- * rename).  A rank-mode handle writes/loads its own strip (one file per rank). */
+ * rename).  A rank-mode handle writes/loads its own strip (one file per rank).  The rule is not
+ * part of the file: the caller restores it (golhip_set_rule). */
 int golhip_checkpoint_save(golhip_t h, const char *path);
 /* Restores the board and turn; GOLHIP_ERR_STATE if the file holds another board or strip. */
 int golhip_checkpoint_load(golhip_t h, const char *path);
 /* Pure host helper: the board size and turn a checkpoint holds (CheckStates' SameSize test). */
 int golhip_checkpoint_info(const char *path, int64_t *width, int64_t *height, int64_t *turn);
+
+/* ---- the rule ---------------------------------------------------------------------------- */
+/* Life-like rules: outer-totalistic on the 8-cell Moore neighbourhood, written B<digits>/S<digits>.
+ * In `birth`, bit n (0..8) means a dead cell with n live neighbours is born; in `survive`, bit n
+ * means a live cell with n live neighbours stays alive.  A handle starts with the reference's rule
+ * (calculateNextState, server/server.go:21-52): B3/S23, birth = 0x008, survive = 0x00C.
+ *
+ * Pure host helper: "B36/S23" (case-insensitive; digits 0-8, either list may be empty: "B2/S")
+ * -> masks.  GOLHIP_ERR_ARG on anything else (digit 9, repeated digit, missing B or S part,
+ * trailing text, NULL); golhip_last_error(NULL) then names the offending text. */
+int golhip_parse_rule(const char *rule, uint32_t *birth, uint32_t *survive);
+/* Set the handle's rule (golhip_set_rule = golhip_parse_rule + golhip_set_rule_masks; masks with
+ * bits above 8: GOLHIP_ERR_ARG).  The board, the turn, flip tracking and every tuning setting are
+ * kept; a change of rule synchronises the handle and drops what is cached per launch shape (captured
+ * graphs, the stable-slab flags).  On failure the handle is untouched and golhip_last_error(h) names
+ * the offending text.  In rank mode every rank sets the same rule.
+ *   - B3/S23, defaulted or set explicitly, runs exactly the kernels and launch plan it always did.
+ *   - Any other rule runs the rule-generic streaming kernel gol_rule on every launch of golhip_step,
+ *     golhip_step_flips, golhip_step_flips_rows, flip tracking and per-turn counts, on single
+ *     strips, golhip_create_strips and both rank modes: golhip_launch_kind* reports kind 5, with
+ *     *param = 1 for a rule with a constant-folded kernel (the catalogue: HighLife B36/S23, Day &
+ *     Night B3678/S34678, Seeds B2/S, Replicator B1357/S1357) and 0 for the table form, which serves
+ *     every other rule and is slower.  Its launches are 8, 4, 2 or 1 generations deep: the largest
+ *     that fits min(k, turns left).  The register slabs, gol_tile, the level split, the whole-board
+ *     kernel, graph replays and stable-slab skipping are bypassed whatever golhip_set_board_kernel /
+ *     golhip_set_activity / golhip_set_graphs say, and golhip_step_persistent returns
+ *     GOLHIP_ERR_STATE before any device work.
+ *   - B0 rules are allowed: the device torus has no dead padding (columns beyond `width` are
+ *     replicas of the board, rows wrap mod height).
+ *   - A checkpoint (GOLCKPT1) does not record the rule: the caller sets it again after
+ *     golhip_checkpoint_load on a new handle. */
+int golhip_set_rule(golhip_t h, const char *rule);
+int golhip_set_rule_masks(golhip_t h, uint32_t birth, uint32_t survive);
+int golhip_get_rule(golhip_t h, uint32_t *birth, uint32_t *survive);
 
 /* ---- the hot path ------------------------------------------------------------------------ */
 /* Advance `turns` generations (Broker.Publish called `turns` times, gol/distributor.go:48-49).
@@ -171,7 +206,8 @@ int golhip_step(golhip_t h, int64_t turns, uint64_t *alive_per_turn);
  * from the largest strip, ceil(height / strips) rows, so every rank of a rank-mode board runs this
  * same sequence (each launch exchanges K-row halos) even when the strips differ by a row.
  * *n = number of entries; depths may be NULL to size the array; GOLHIP_ERR_CAP if cap is too
- * small. */
+ * small.  It takes no handle and always describes the B3/S23 plan (another rule runs 8 / 4 / 2 / 1
+ * deep launches of gol_rule, see golhip_set_rule). */
 int golhip_launch_plan(int64_t width, int64_t height, int strips, int k, int64_t turns,
                        int32_t *depths, size_t cap, size_t *n);
 /* Alive cells of the whole board (COLLECTIVE: sums over ranks). */
@@ -227,7 +263,9 @@ int golhip_set_tail_bands(golhip_t h, int bands, int rows);
  * (gol_stencil, gol_step1 at k = 1), 1 the level-split kernel (*param = waves per band), 2 the
  * register-tile kernel gol_tile (*param = tile height T), 3 the register-slab kernel gol_slab
  * (*param = [10000 * row chains +] 100 * waves + rows per wave), 4 the whole-board kernel gol_board
- * (*param = 100 * waves + rows per segment; golhip_set_board_kernel).  Introspection for tests and the
+ * (*param = 100 * waves + rows per segment; golhip_set_board_kernel), 5 the rule-generic streaming
+ * kernel gol_rule of every rule but B3/S23 (*param = 1 constant-folded, 0 table form; golhip_set_rule).
+ * Introspection for tests and the
  * bench line.  golhip_launch_kind describes a launch without per-generation counts,
  * golhip_launch_kind_counts one with (counting != 0) or without them: small boards pick a
  * different slab shape when counting. */
