@@ -6,6 +6,7 @@
 //                       count reductions, the RCCL fail-fast waits, golhip_create_rank*
 //   engine_cells.hip    alive-cell lists and CellFlipped extraction, the per-turn flips ring
 //   engine_io.hip       host transfers (PGM bytes, uint64 words, random init) and checkpoints
+//   engine_view.hip     windowed access: a rectangle as bytes (out / in) and the density viewport
 // The tuning library adds tuning/engine_tuning.hip, which registers engine_hooks(); the production
 // library has no hooks (every hook pointer below stays null there).
 //
@@ -37,7 +38,7 @@
 
 namespace golhip {
 
-constexpr int kVersion = 103;  // 103: golhip_set_persistent_limit / _handoff (round 6)
+constexpr int kVersion = 104;  // 104: golhip_store_rect / _load_rect / _view_counts / _view
 // Generations of per-turn counts finalized per launch (golhip_set_count_window changes it; at
 // least the graph length kGraphGens: tests shrink it to exercise flushes).
 constexpr int kCountWindowDefault = 4096;

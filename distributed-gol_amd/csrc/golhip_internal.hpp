@@ -332,4 +332,20 @@ hipError_t launch_words_out(const uint32_t *row0, int64_t pitch, int64_t rows, i
 hipError_t launch_words_in(const uint64_t *words, int64_t rows, int64_t width, int32_t wd,
                            uint32_t *row0, int64_t pitch, hipStream_t s);
 
+// ---- windowed access (view_kernels.hip) --------------------------------------------------------
+// x0 is a logical column in [0, width); columns past it are taken mod the torus (wd words).
+// The density viewport: out[jj * w + i] = live cells of the scale x scale block whose columns are
+// x0 + i * scale onward and whose rows are rows [jj * scale - phase, + scale) of the `nrows` rows at
+// rows0, clipped to them (a pixel row cut by the end of a strip gives a partial count); npr pixel
+// rows, scale a power of two in 1..1024, phase < scale.
+hipError_t launch_view_counts(const uint32_t *rows0, int64_t pitch, int64_t nrows, int32_t phase, int32_t wd,
+                              int64_t x0, int32_t scale, int32_t w, int64_t npr, uint32_t *out, hipStream_t s);
+// Columns [x0, x0 + w) of packed rows -> 0/255 bytes (compact, stride == w).
+hipError_t launch_rect_unpack(const uint32_t *row0, int64_t pitch, int64_t rows, int32_t wd, int64_t x0,
+                              int64_t w, uint8_t *bytes, hipStream_t s);
+// 0/nonzero bytes (compact, stride == w) into columns [x0, x0 + w) of packed rows, in every
+// horizontal replica of the torus: mode 0 copy, 1 or, 2 xor (a masked read-modify-write).
+hipError_t launch_rect_pack(const uint8_t *bytes, int64_t rows, int64_t width, int32_t wd, int64_t x0, int64_t w,
+                            int mode, uint32_t *row0, int64_t pitch, hipStream_t s);
+
 }  // namespace golhip

@@ -716,6 +716,10 @@ __global__ __launch_bounds__(64 * W) void gol_slab2(const uint32_t *__restrict__
                     golhip::store_row<1, false>(orsrc, ls, v, o >= 0 && o < nrows ? o * rowbytes : kOutOfRange);
                 }
             }
+            // every wave has read `same` before wave 0 sets it below (the skip is taken by the whole
+            // workgroup: all waves test the same flags).  Without this a wave that read it late saw
+            // 1 and kept its rows of an older generation in the output buffer
+            __syncthreads();
             if (w == 0) {  // vector stores / atomics from lanes, never the scalar path
                 if constexpr (COUNT) {
                     const uint32_t n = __builtin_amdgcn_readlane(wave_sum_dpp(lane < W ? pop[lane] : 0u), 63);

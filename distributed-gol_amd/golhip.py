@@ -35,6 +35,8 @@ ERR_ARG, ERR_HIP, ERR_OOM, ERR_CAP, ERR_RCCL, ERR_NODEV, ERR_STATE = -1, -2, -3,
 NCCL_ID_BYTES = 128
 DENSITY_HALF = 0x80000000
 HANDOFF_FENCED, HANDOFF_SC1 = 0, 1  # golhip_set_persistent_handoff
+RECT_COPY, RECT_OR, RECT_XOR = 0, 1, 2  # golhip_load_rect
+_RECT_MODES = {"copy": RECT_COPY, "or": RECT_OR, "xor": RECT_XOR}
 
 # Every symbol include/golhip.h declares (tests/test_boundary.py checks the .so exports them).
 EXPORTS = [
@@ -54,6 +56,7 @@ EXPORTS = [
     "golhip_step_flips_rows", "golhip_flips_fetch_rows",
     "golhip_checkpoint_save", "golhip_checkpoint_load", "golhip_checkpoint_info",
     "golhip_parse_rule", "golhip_set_rule", "golhip_set_rule_masks", "golhip_get_rule",
+    "golhip_store_rect", "golhip_load_rect", "golhip_view_counts", "golhip_view",
 ]
 
 
@@ -223,6 +226,10 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
         "golhip_set_rule": ([H, ctypes.c_char_p], i32),
         "golhip_set_rule_masks": ([H, ctypes.c_uint32, ctypes.c_uint32], i32),
         "golhip_get_rule": ([H, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)], i32),
+        "golhip_store_rect": ([H, i64, i64, i64, i64, ctypes.c_void_p, ctypes.c_size_t], i32),
+        "golhip_load_rect": ([H, i64, i64, i64, i64, ctypes.c_void_p, ctypes.c_size_t, i32], i32),
+        "golhip_view_counts": ([H, i64, i64, i64, i64, i32, ctypes.c_void_p], i32),
+        "golhip_view": ([H, i64, i64, i64, i64, i32, ctypes.c_void_p, ctypes.c_size_t], i32),
         "golhip_launch_kind": ([H, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], i32),
         "golhip_launch_kind_counts": ([H, i32, i32, ctypes.POINTER(ctypes.c_int),
                                        ctypes.POINTER(ctypes.c_int)], i32),
@@ -498,6 +505,43 @@ class Engine:
         words = np.ascontiguousarray(words, dtype=np.uint64)
         assert words.shape == (self.info.rows, self.info.width // 64)
         self._check(self._L.golhip_load_words(self._h, words.ctypes.data))
+
+    # -- windowed access (global coordinates, any int, wrapping round the torus)
+    def store_rect(self, x: int, y: int, w: int, h: int) -> np.ndarray:
+        """golhip_store_rect: the w x h rectangle whose top-left cell is (x, y), 0/255 uint8 (h, w)."""
+        out = np.empty((max(h, 0), max(w, 0)), dtype=np.uint8)
+        self._check(self._L.golhip_store_rect(self._h, x, y, w, h, out.ctypes.data, max(w, 0)))
+        return out
+
+    def load_rect(self, x: int, y: int, cells: np.ndarray, mode: str | int = "copy"):
+        """golhip_load_rect: write 0/nonzero `cells` (h, w) into the running board at (x, y) --
+        mode "copy" / "or" / "xor" (or RECT_*).  The turn is kept."""
+        cells = np.ascontiguousarray(cells, dtype=np.uint8)
+        assert cells.ndim == 2, cells.shape
+        m = _RECT_MODES[mode] if isinstance(mode, str) else int(mode)
+        self._check(self._L.golhip_load_rect(self._h, x, y, cells.shape[1], cells.shape[0],
+                                             cells.ctypes.data, cells.strides[0], m))
+
+    def place(self, pattern: np.ndarray, x: int, y: int, mode: str | int = "or"):
+        """Stamp a pattern (parse_rle's 0/255 array) at (x, y) on the device board: the module's
+        place() for the running board, without reloading it."""
+        self.load_rect(x, y, pattern, mode)
+
+    def view_counts(self, x: int, y: int, w: int, h: int, scale: int, out: np.ndarray | None = None) -> np.ndarray:
+        """golhip_view_counts: uint32 (h, w), pixel (j, i) = live cells of the scale x scale block
+        whose top-left cell is (x + i*scale, y + j*scale).  out: a C-contiguous uint32 (h, w) array to
+        fill instead of a new one (a display loop reuses one, page-locked: pinned_empty)."""
+        if out is None:
+            out = np.empty((max(h, 0), max(w, 0)), dtype=np.uint32)
+        assert out.dtype == np.uint32 and out.shape == (h, w) and out.flags.c_contiguous
+        self._check(self._L.golhip_view_counts(self._h, x, y, w, h, scale, out.ctypes.data))
+        return out
+
+    def view(self, x: int, y: int, w: int, h: int, scale: int) -> np.ndarray:
+        """golhip_view: the viewport as grey uint8 (h, w), ceil(255 * count / scale^2)."""
+        out = np.empty((max(h, 0), max(w, 0)), dtype=np.uint8)
+        self._check(self._L.golhip_view(self._h, x, y, w, h, scale, out.ctypes.data, max(w, 0)))
+        return out
 
     # -- the rule
     def set_rule(self, rule: str | tuple[int, int]):

@@ -40,6 +40,30 @@ public:
         check(golhip_store_bytes(h_, out.data(), (size_t)info_.width));
         return out;
     }
+    // Windowed access (global coordinates, wrapping round the torus): a rectangle as 0/255 bytes,
+    // out and into the running board (mode GOLHIP_RECT_*), and the density viewport, one pixel per
+    // scale x scale block of cells, as counts or as grey (ceil(255 * count / scale^2)).
+    std::vector<uint8_t> store_rect(int64_t x, int64_t y, int64_t w, int64_t h) {
+        std::vector<uint8_t> out((size_t)std::max<int64_t>(w, 0) * (size_t)std::max<int64_t>(h, 0));
+        check(golhip_store_rect(h_, x, y, w, h, out.data(), (size_t)std::max<int64_t>(w, 0)));
+        return out;
+    }
+    void load_rect(int64_t x, int64_t y, int64_t w, int64_t h, const std::vector<uint8_t> &cells,
+                   int mode = GOLHIP_RECT_COPY) {
+        if (w > 0 && h > 0 && cells.size() < (size_t)w * (size_t)h)
+            throw EngineError(GOLHIP_ERR_ARG, "load_rect: fewer cells than w * h");
+        check(golhip_load_rect(h_, x, y, w, h, cells.data(), (size_t)std::max<int64_t>(w, 0), mode));
+    }
+    std::vector<uint32_t> view_counts(int64_t x, int64_t y, int64_t w, int64_t h, int scale) {
+        std::vector<uint32_t> out((size_t)std::max<int64_t>(w, 0) * (size_t)std::max<int64_t>(h, 0));
+        check(golhip_view_counts(h_, x, y, w, h, scale, out.data()));
+        return out;
+    }
+    std::vector<uint8_t> view(int64_t x, int64_t y, int64_t w, int64_t h, int scale) {
+        std::vector<uint8_t> out((size_t)std::max<int64_t>(w, 0) * (size_t)std::max<int64_t>(h, 0));
+        check(golhip_view(h_, x, y, w, h, scale, out.data(), (size_t)std::max<int64_t>(w, 0)));
+        return out;
+    }
     // Advance `turns`; returns the alive count after each turn when `counts`.
     std::vector<uint64_t> step(int64_t turns, bool counts) {
         std::vector<uint64_t> c(counts ? (size_t)turns : 0);

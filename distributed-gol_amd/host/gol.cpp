@@ -278,9 +278,14 @@ std::string board_name(const Params &p) {
     return std::to_string(p.ImageWidth) + "x" + std::to_string(p.ImageHeight);
 }
 
-void snapshot(Engine &eng, const Params &p, const RunOptions &o, const std::string &name) {
+// out/<name>.pgm, and with a viewport (RunOptions::view) out/<name>-view.pgm after it.
+void snapshot(Engine &eng, const Params &p, const RunOptions &o, const std::string &name, const ViewSpec *view) {
     Image img{p.ImageWidth, p.ImageHeight, eng.store()};
     write_pgm(o.out_dir + "/" + name + ".pgm", img);
+    if (view) {
+        Image v{(int)view->w, (int)view->h, eng.view(view->x, view->y, view->w, view->h, view->scale)};
+        write_pgm(o.out_dir + "/" + name + "-view.pgm", v);
+    }
 }
 
 bool file_exists(const std::string &path) {
@@ -302,6 +307,26 @@ std::string checkpoint_file(const RunOptions &o) {
 
 void reset_saved_state(const RunOptions &o) { std::remove(checkpoint_file(o).c_str()); }
 
+ViewSpec parse_view_spec(const std::string &spec, int width, int height) {
+    auto bad = [&](const std::string &why) {
+        return std::runtime_error("view \"" + spec + "\": " + why);
+    };
+    long long v[5];
+    int used = 0;
+    if (std::sscanf(spec.c_str(), "%lld,%lld,%lld,%lld,%lld%n", &v[0], &v[1], &v[2], &v[3], &v[4], &used) != 5 ||
+        (size_t)used != spec.size())
+        throw bad("expected x,y,w,h,scale");
+    ViewSpec s;
+    s.x = v[0], s.y = v[1], s.w = v[2], s.h = v[3];
+    if (v[4] < 1 || v[4] > 1024 || (v[4] & (v[4] - 1))) throw bad("scale is not a power of two in 1..1024");
+    s.scale = (int)v[4];
+    if (s.w < 1 || s.h < 1) throw bad("w and h must be at least 1");
+    if (s.w > width / s.scale || s.h > height / s.scale)
+        throw bad("w * scale and h * scale must fit the " + std::to_string(width) + "x" + std::to_string(height) +
+                  " board");
+    return s;
+}
+
 void Run(Params p, Channel<Event> *events, Channel<char> *keyPresses, const RunOptions &o) {
     // A failure (EngineError, I/O) ends the run the way the reference's controller ends: the
     // events channel is closed so consumers see the end, then the error propagates.
@@ -318,6 +343,13 @@ namespace {
 void run_impl(const Params &p, Channel<Event> *events, Channel<char> *keyPresses,
               const RunOptions &o) {
     const std::string name = board_name(p);
+    // a viewport the board cannot satisfy ends the run here, before any engine exists
+    ViewSpec view_spec;
+    const ViewSpec *view = nullptr;
+    if (!o.view.empty()) {
+        view_spec = parse_view_spec(o.view, p.ImageWidth, p.ImageHeight);
+        view = &view_spec;
+    }
     Image img = read_pgm(o.image_dir + "/" + name + ".pgm");
     if (img.width != p.ImageWidth) throw std::runtime_error("Incorrect width");
     if (img.height != p.ImageHeight) throw std::runtime_error("Incorrect height");
@@ -362,8 +394,9 @@ void run_impl(const Params &p, Channel<Event> *events, Channel<char> *keyPresses
         switch (key) {
             case 's': {
                 const std::string f = name + "x" + std::to_string(turn);
-                snapshot(*eng, p, o, f);
+                snapshot(*eng, p, o, f, view);
                 pipe.event(Event::image_output_complete(turn, f));
+                if (view) pipe.event(Event::image_output_complete(turn, f + "-view"));
                 break;
             }
             case 'q': {
@@ -376,8 +409,9 @@ void run_impl(const Params &p, Channel<Event> *events, Channel<char> *keyPresses
             }
             case 'k': {
                 const std::string f = name + "x" + std::to_string(turn);
-                snapshot(*eng, p, o, f);
+                snapshot(*eng, p, o, f, view);
                 pipe.event(Event::image_output_complete(turn, f));
+                if (view) pipe.event(Event::image_output_complete(turn, f + "-view"));
                 pipe.event(Event::state_change(turn, State::Quitting));
                 eng.reset();  // Broker.Quit -> GolOP.Quit: the workers go away
                 reset_saved_state(o);
@@ -440,7 +474,10 @@ void run_impl(const Params &p, Channel<Event> *events, Channel<char> *keyPresses
     pipe.finish();
     ticker.halt();
     events->send(Event::final_turn_complete(turn, std::move(alive)));
-    snapshot(*eng, p, o, name + "x" + std::to_string(p.Turns));  // out/WxHxT.pgm (:246-253)
+    const std::string last = name + "x" + std::to_string(p.Turns);
+    snapshot(*eng, p, o, last, view);  // out/WxHxT.pgm (:246-253)
+    // Run sends no ImageOutputComplete for the final PGM; the viewport that follows it has one
+    if (view) events->send(Event::image_output_complete(turn, last + "-view"));
     events->send(Event::state_change(turn, State::Quitting));   // :259
     events->close();                                             // :262
 }

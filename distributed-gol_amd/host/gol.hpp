@@ -108,7 +108,20 @@ struct RunOptions {
     // after a resume: the checkpoint does not record it.  Default: the reference's rule
     // (server/server.go:21-52).
     std::string rule = "B3/S23";
+    // A viewport "x,y,w,h,scale" (golhip_view: pixel (i, j) is the scale x scale block of cells at
+    // (x + i*scale, y + j*scale), grey = ceil(255 * live / scale^2)).  When set, every PGM the run
+    // writes is followed by <out_dir>/<W>x<H>x<turn>-view.pgm, w x h -- the window on a board too
+    // large to look at whole (sdl/loop.go shows the world one pixel per cell).  Empty: none.
+    std::string view;
 };
+
+// RunOptions::view parsed and checked against the board: scale a power of two in 1..1024,
+// 1 <= w, h, w * scale <= width, h * scale <= height.  Throws std::runtime_error naming the spec.
+struct ViewSpec {
+    int64_t x = 0, y = 0, w = 0, h = 0;
+    int scale = 1;
+};
+ViewSpec parse_view_spec(const std::string &spec, int width, int height);
 
 // gol/gol.go:14 -- runs the whole simulation, sends events, closes `events` at the end.
 // keyPresses may be null (the tests pass nil, gol_test.go:34).

@@ -2,12 +2,16 @@
 //   -t threads  -w width  -h height  -turns N  -noVis (always headless: SDL is out of scope)
 //   extra: -gpus G (row strips), -k K (max generations per launch), -images DIR, -out DIR,
 //          -checkpoint PATH (the 'q' state file; default OUT/broker_state.ckpt), -flips,
-//          -rule B36/S23 (a life-like rule; default B3/S23; a bad rule exits with status 2)
+//          -rule B36/S23 (a life-like rule; default B3/S23; a bad rule exits with status 2),
+//          -view x,y,w,h,scale (every PGM written is followed by OUT/<W>x<H>x<turn>-view.pgm, the
+//          w x h viewport at (x, y) with one grey pixel per scale x scale cells; a spec that is
+//          malformed or does not fit the board exits with status 2 before any engine is created)
 // Keys p/s/q/k are read from stdin (one character per line), like the SDL key loop
 // (sdl/loop.go:17-27) would deliver them.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
 #include <iostream>
 #include <string>
 #include <thread>
@@ -19,6 +23,7 @@ int main(int argc, char **argv) {
     gol::Params p{10000000000LL, 8, 512, 512};  // main.go:38-42 defaults: 8 threads, 512x512, 1e10 turns
     gol::RunOptions o;
     o.flip_events = false;
+    bool view_set = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : "0"; };
@@ -33,7 +38,19 @@ int main(int argc, char **argv) {
         else if (a == "-checkpoint") o.checkpoint_path = next();
         else if (a == "-flips") o.flip_events = true;
         else if (a == "-rule") o.rule = i + 1 < argc ? argv[++i] : "";
+        else if (a == "-view") {
+            o.view = i + 1 < argc ? argv[++i] : "";
+            view_set = true;
+        }
         else if (a == "-noVis") {}
+    }
+    if (view_set) {  // checked against the board before any engine exists
+        try {
+            gol::parse_view_spec(o.view, p.ImageWidth, p.ImageHeight);
+        } catch (const std::exception &e) {
+            std::fprintf(stderr, "gol: %s\n", e.what());
+            return 2;
+        }
     }
     if (uint32_t b = 0, s = 0; golhip_parse_rule(o.rule.c_str(), &b, &s) != GOLHIP_OK) {
         std::fprintf(stderr, "gol: %s\n", golhip_last_error(nullptr));

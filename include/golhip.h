@@ -142,6 +142,54 @@ int golhip_store_bytes(golhip_t h, uint8_t *out, size_t row_stride);
 int golhip_store_words(golhip_t h, uint64_t *out);
 int golhip_load_words(golhip_t h, const uint64_t *in);
 
+/* ---- windowed access: a rectangle of the board, and a density viewport ----------------------
+ * The reference shows the world in an SDL window, one pixel per cell (sdl/loop.go, sdl/window.go),
+ * and its `s` key writes the whole world as a PGM (gol/distributor.go:93-103).  At 65536^2 neither
+ * can be used (nobody displays 65536^2 pixels; the PGM is 4 GiB), so these calls move only a window:
+ * a rectangle of cells as bytes, out and in, and a viewport in which one pixel stands for a
+ * scale x scale block of cells.  Their cost follows the window, not the board.
+ *   - Coordinates are GLOBAL board coordinates.  x and y may be any int64 and are taken mod width /
+ *     height; the rectangle wraps round the torus in both directions.  1 <= w <= width and
+ *     1 <= hgt <= height.
+ *   - The viewport: scale is a power of two in 1..1024, w * scale <= width and hgt * scale <= height
+ *     (no cell is covered twice).
+ *   - Anything else, a null buffer, row_stride < w or a mode outside 0..2 is GOLHIP_ERR_ARG: the
+ *     board is untouched and golhip_last_error names the offending value.
+ *   - All four synchronise the handle first, as golhip_store_bytes does (in rank mode within the
+ *     comm timeout).  None allocates device memory: they stage through the transfer stage in chunks.
+ *   - A handle that owns several strips (golhip_create, golhip_create_strips) serves each row from
+ *     the strip that holds it; a viewport block that straddles two strips is the sum of their parts.
+ *   - A handle that does NOT hold every row (rank mode, world_size > 1): the calls are not
+ *     collective.  golhip_store_rect and golhip_view_counts write `out` in full, cells of rows the
+ *     handle does not hold reading as dead, so the ranks' results combine by OR / by sum;
+ *     golhip_load_rect ignores rows it does not hold (every rank passes the same rectangle);
+ *     golhip_view returns GOLHIP_ERR_STATE (a partial count has no grey value: reduce the counts).
+ *   - They do not depend on the rule (golhip_set_rule). */
+#define GOLHIP_RECT_COPY 0 /* rectangle := cells */
+#define GOLHIP_RECT_OR 1   /* rectangle |= cells */
+#define GOLHIP_RECT_XOR 2  /* rectangle ^= cells */
+/* Cells of the w x hgt rectangle whose top-left cell is (x, y), as 0/255 bytes
+ * (out[j * row_stride + i] = cell (x + i, y + j)). */
+int golhip_store_rect(golhip_t h, int64_t x, int64_t y, int64_t w, int64_t hgt, uint8_t *out,
+                      size_t row_stride);
+/* Write 0/nonzero bytes into that rectangle of the RUNNING board (drop a pattern in): a change to
+ * the board, not a new board, so the turn is kept.  What was derived from the old cells is dropped:
+ * golhip_flips returns GOLHIP_ERR_STATE until the next step, and no stable slab is skipped on the
+ * strength of flags from before the change (golhip_set_activity).  Captured graphs stay valid (the
+ * same buffers and parity).  Only rows the handle owns are written; halo rows are exchanged again at
+ * the start of the next step block, as after golhip_load_bytes. */
+int golhip_load_rect(golhip_t h, int64_t x, int64_t y, int64_t w, int64_t hgt, const uint8_t *cells,
+                     size_t row_stride, int mode);
+/* Viewport: pixel (i, j) of the w x hgt output covers the scale x scale block of cells whose
+ * top-left cell is (x + i*scale, y + j*scale); out[j*w + i] = live cells in it. */
+int golhip_view_counts(golhip_t h, int64_t x, int64_t y, int64_t w, int64_t hgt, int scale,
+                       uint32_t *out /* w*hgt, dense */);
+/* The same as a grey image: grey = (count*255 + scale*scale - 1) / (scale*scale), i.e.
+ * ceil(255 * count / scale^2): an empty block is 0, any live cell at least 1, a full block 255.
+ * At scale 1 it equals golhip_store_rect. */
+int golhip_view(golhip_t h, int64_t x, int64_t y, int64_t w, int64_t hgt, int scale, uint8_t *out,
+                size_t row_stride);
+
 /* ---- checkpoint: the broker's paused state (broker/broker.go:124-155) ---------------------
  * The reference keeps worldSave/turn/size in the broker process between controller runs ('q'
  * sends Pause{P: true, Turn, Dimension}; the next controller's CheckStates resumes when the size
