@@ -1,0 +1,328 @@
+// engine_batch.hip -- golhip_batch: many independent small tori on one device, a second handle
+// type beside the engine (golhip_engine.hip).
+//
+// The reference runs one world per broker (broker/broker.go:157-180); a soup search, a seed or
+// density sweep or a census runs thousands of small ones.  A batch holds nboards tori of one size
+// -- the sizes of the whole-board kernel, stencil_board_shape: 4, 8 or 16 torus words wide, 4 W R
+// rows -- back to back in one allocation, board i at boards + i * height * wd words in the packed
+// layout of a single engine of that size, and advances all of them with one gol_batch launch per
+// <= kBoardMaxK generations (batch_board.hip: one workgroup per board, in place).  Always B3/S23.
+//
+// Device memory is allocated at create (the boards, the per-board counters, the transfer stage) and
+// by the first golhip_batch_track_settle(b, 1) (board(t - 1) of every board); no other call
+// allocates.  Bytes in and out, the seeds of init_random, per-board counts and the per-turn
+// history all pass through the stage in chunks.
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include "golhip_engine.hpp"
+
+struct golhip_batch {
+    int64_t width = 0, height = 0, L = 0;
+    int32_t wd = 0;
+    int W = 0, R = 0;  // the kernel's shape: 4 W R == height
+    int nboards = 0, device = 0;
+    int64_t board_words = 0;  // height * wd
+    hipStream_t stream = nullptr;
+    uint32_t *boards = nullptr;
+    uint32_t *prev = nullptr;                 // settle tracking: board(turn - 1) of every board
+    unsigned long long *last_diff = nullptr;  // last turn t with board(t) != board(t - 2); 0: none yet
+    uint8_t *stage = nullptr;
+    int64_t stage_bytes = 0;
+    bool track = false;
+    int64_t turn = 0;
+    std::string err;
+};
+
+namespace golhip {
+namespace {
+
+int bfail(golhip_batch_t b, int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (b)
+        b->err = buf;
+    else
+        g_create_error = buf;
+    return code;
+}
+
+#define BHIPCHK(b, expr)                                                                          \
+    do {                                                                                          \
+        hipError_t e_ = (expr);                                                                   \
+        if (e_ != hipSuccess)                                                                     \
+            return bfail((b), e_ == hipErrorOutOfMemory ? GOLHIP_ERR_OOM : GOLHIP_ERR_HIP,         \
+                         "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);     \
+    } while (0)
+
+void batch_free(golhip_batch_t b) {
+    if (hipSetDevice(b->device) != hipSuccess) return;
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    if (b->boards) (void)hipFree(b->boards);
+    if (b->prev) (void)hipFree(b->prev);
+    if (b->last_diff) (void)hipFree(b->last_diff);
+    if (b->stage) (void)hipFree(b->stage);
+    if (b->stream) (void)hipStreamDestroy(b->stream);
+    b->boards = b->prev = nullptr;
+    b->last_diff = nullptr;
+    b->stage = nullptr;
+    b->stream = nullptr;
+}
+
+int batch_alloc(golhip_batch_t b) {
+    BHIPCHK(b, hipSetDevice(b->device));
+    hipDeviceProp_t prop;
+    BHIPCHK(b, hipGetDeviceProperties(&prop, b->device));
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return bfail(b, GOLHIP_ERR_NODEV, "device %d is %s, libgolhip is built for gfx950", b->device,
+                     prop.gcnArchName);
+    BHIPCHK(b, hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    const size_t bytes = sizeof(uint32_t) * (size_t)b->board_words * (size_t)b->nboards;
+    BHIPCHK(b, hipMalloc(&b->boards, bytes));
+    BHIPCHK(b, hipMemsetAsync(b->boards, 0, bytes, b->stream));
+    // the stage: every board as bytes if that fits in kStageBytes (GOLHIP_STAGE_BYTES, read at
+    // create, shrinks it: tests force chunked transfers and several launches per history call);
+    // never less than one byte row or one uint32 per board (a generation of history, the counts)
+    int64_t cap = kStageBytes;
+    if (const char *e = std::getenv("GOLHIP_STAGE_BYTES")) cap = std::max<int64_t>(1, std::atoll(e));
+    const int64_t floor_bytes = std::max<int64_t>(b->width, 4 * (int64_t)b->nboards);
+    b->stage_bytes = std::max<int64_t>(floor_bytes, std::min<int64_t>(cap, b->width * b->height * b->nboards));
+    BHIPCHK(b, hipMalloc(&b->stage, (size_t)b->stage_bytes));
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    return GOLHIP_OK;
+}
+
+// A new set of boards: turn 0, no settle record.
+int boards_replaced(golhip_batch_t b) {
+    b->turn = 0;
+    if (b->last_diff)
+        BHIPCHK(b, hipMemsetAsync(b->last_diff, 0, sizeof(unsigned long long) * (size_t)b->nboards, b->stream));
+    return GOLHIP_OK;
+}
+
+// Boards [first, first + n) <-> host bytes, as one tall array of n * height byte rows cut into
+// chunks the stage holds; a chunk is copied in one piece where the host rows are dense, else one
+// 2-D copy per board it touches.
+int transfer(golhip_batch_t b, int first, int n, uint8_t *host, size_t row_stride, size_t board_stride,
+             bool to_device) {
+    if (!host) return bfail(b, GOLHIP_ERR_ARG, "buffer is null");
+    if (first < 0 || n < 1 || (int64_t)first + n > b->nboards)
+        return bfail(b, GOLHIP_ERR_ARG, "boards [%d, %lld) outside the batch's %d boards", first,
+                     (long long)first + n, b->nboards);
+    const int64_t W = b->width, H = b->height;
+    if (row_stride < (size_t)W) return bfail(b, GOLHIP_ERR_ARG, "row_stride %zu < width %lld", row_stride, (long long)W);
+    if (board_stride < (size_t)(H - 1) * row_stride + (size_t)W)
+        return bfail(b, GOLHIP_ERR_ARG, "board_stride %zu < the %lld rows of a board", board_stride, (long long)H);
+    BHIPCHK(b, hipSetDevice(b->device));
+    const bool dense = row_stride == (size_t)W && board_stride == (size_t)(W * H);
+    const int64_t rows = (int64_t)n * H, cr = std::max<int64_t>(1, b->stage_bytes / W);
+    for (int64_t r0 = 0; r0 < rows; r0 += cr) {
+        const int64_t nr = std::min(cr, rows - r0);
+        uint32_t *dev = b->boards + (int64_t)first * b->board_words + r0 * b->wd;
+        if (!to_device) BHIPCHK(b, launch_unpack(dev, b->wd, nr, W, b->stage, b->stream));
+        for (int64_t r = r0; r < r0 + nr;) {  // the chunk's rows, board by board
+            const int64_t bi = r / H, y = r - bi * H;
+            const int64_t m = dense ? nr : std::min(H - y, r0 + nr - r);
+            uint8_t *hp = host + (size_t)bi * board_stride + (size_t)y * row_stride;
+            uint8_t *sp = b->stage + (r - r0) * W;
+            if (to_device)
+                BHIPCHK(b, hipMemcpy2DAsync(sp, (size_t)W, hp, row_stride, (size_t)W, (size_t)m, hipMemcpyHostToDevice,
+                                            b->stream));
+            else
+                BHIPCHK(b, hipMemcpy2DAsync(hp, row_stride, sp, (size_t)W, (size_t)W, (size_t)m, hipMemcpyDeviceToHost,
+                                            b->stream));
+            r += m;
+        }
+        if (to_device) BHIPCHK(b, launch_pack(b->stage, nr, W, b->wd, dev, b->wd, b->stream));
+        BHIPCHK(b, hipStreamSynchronize(b->stream));
+    }
+    return GOLHIP_OK;
+}
+
+}  // namespace
+}  // namespace golhip
+
+using namespace golhip;
+
+// ================================================================================ C ABI ====
+extern "C" {
+
+int golhip_batch_create(int width, int height, int nboards, int device, golhip_batch_t *out) {
+    if (!out) return bfail(nullptr, GOLHIP_ERR_ARG, "out is null");
+    *out = nullptr;
+    int W = 0, R = 0;
+    const int64_t L = width >= 1 && width <= 512 ? lcm64(width, 128) : 0;
+    if (L != 128 && L != 256 && L != 512)
+        return bfail(nullptr, GOLHIP_ERR_ARG,
+                     "batch width %d: the torus lcm(width, 128) must be 128, 256 or 512 cells wide", width);
+    if (!stencil_board_shape(height, (int32_t)(L / 32), &W, &R))
+        return bfail(nullptr, GOLHIP_ERR_ARG, "batch height %d: one of 4, 8, 16, 32, 64, 128, 256, 512 rows", height);
+    if (nboards < 1) return bfail(nullptr, GOLHIP_ERR_ARG, "batch nboards %d: at least 1", nboards);
+    if (device < 0) return bfail(nullptr, GOLHIP_ERR_ARG, "batch device %d", device);
+    golhip_batch *b = new golhip_batch;
+    b->width = width;
+    b->height = height;
+    b->L = L;
+    b->wd = (int32_t)(L / 32);
+    b->W = W;
+    b->R = R;
+    b->nboards = nboards;
+    b->device = device;
+    b->board_words = (int64_t)height * b->wd;
+    const int rc = batch_alloc(b);
+    if (rc) {
+        g_create_error = b->err;
+        batch_free(b);  // nothing is leaked
+        delete b;
+        return rc;
+    }
+    *out = b;
+    return GOLHIP_OK;
+}
+
+int golhip_batch_destroy(golhip_batch_t b) {
+    if (!b) return GOLHIP_ERR_ARG;
+    batch_free(b);
+    delete b;
+    return GOLHIP_OK;
+}
+
+const char *golhip_batch_last_error(golhip_batch_t b) { return b ? b->err.c_str() : g_create_error.c_str(); }
+
+int golhip_batch_load_bytes(golhip_batch_t b, int first, int n, const uint8_t *cells, size_t row_stride,
+                            size_t board_stride) {
+    if (!b) return GOLHIP_ERR_ARG;
+    const int rc = transfer(b, first, n, const_cast<uint8_t *>(cells), row_stride, board_stride, true);
+    if (rc) return rc;
+    return boards_replaced(b);
+}
+
+int golhip_batch_store_bytes(golhip_batch_t b, int first, int n, uint8_t *out, size_t row_stride,
+                             size_t board_stride) {
+    if (!b) return GOLHIP_ERR_ARG;
+    return transfer(b, first, n, out, row_stride, board_stride, false);
+}
+
+int golhip_batch_init_random(golhip_batch_t b, const uint64_t *seeds, uint64_t seed0, uint32_t density_q32) {
+    if (!b) return GOLHIP_ERR_ARG;
+    if (b->width % 64 != 0)
+        return bfail(b, GOLHIP_ERR_ARG, "init_random needs width %% 64 == 0 (width %lld)", (long long)b->width);
+    BHIPCHK(b, hipSetDevice(b->device));
+    if (!seeds) {
+        BHIPCHK(b, launch_batch_init_random(b->boards, b->board_words, b->nboards, b->height, b->width, b->wd,
+                                            nullptr, seed0, density_q32, b->stream));
+    } else {  // the seeds through the stage, a chunk of boards at a time
+        uint64_t *dseeds = reinterpret_cast<uint64_t *>(b->stage);
+        const int64_t cb = std::max<int64_t>(1, b->stage_bytes / (int64_t)sizeof(uint64_t));
+        for (int64_t i = 0; i < b->nboards; i += cb) {
+            const int64_t nb = std::min<int64_t>(cb, b->nboards - i);
+            BHIPCHK(b, hipMemcpyAsync(dseeds, seeds + i, sizeof(uint64_t) * (size_t)nb, hipMemcpyHostToDevice,
+                                      b->stream));
+            BHIPCHK(b, launch_batch_init_random(b->boards + i * b->board_words, b->board_words, nb, b->height,
+                                                b->width, b->wd, dseeds, 0, density_q32, b->stream));
+            BHIPCHK(b, hipStreamSynchronize(b->stream));
+        }
+    }
+    const int rc = boards_replaced(b);
+    if (rc) return rc;
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    return GOLHIP_OK;
+}
+
+int golhip_batch_step(golhip_batch_t b, int64_t turns, uint32_t *history, size_t board_stride) {
+    if (!b) return GOLHIP_ERR_ARG;
+    if (turns < 0) return bfail(b, GOLHIP_ERR_ARG, "turns %lld < 0", (long long)turns);
+    if (turns == 0) return GOLHIP_OK;
+    if (history && board_stride < (size_t)turns)
+        return bfail(b, GOLHIP_ERR_ARG, "board_stride %zu < turns %lld", board_stride, (long long)turns);
+    BHIPCHK(b, hipSetDevice(b->device));
+    // a launch is at most kBoardMaxK deep, and with history no deeper than the stage holds counts
+    // for: nboards * K * 4 bytes
+    int64_t kmax = kBoardMaxK;
+    if (history) kmax = std::max<int64_t>(1, std::min<int64_t>(kmax, b->stage_bytes / (4 * (int64_t)b->nboards)));
+    BatchParams p{};
+    p.boards = b->boards;
+    p.board_pitch = b->board_words;
+    p.wd = b->wd;
+    p.width = (int32_t)b->width;
+    p.hist = history ? reinterpret_cast<uint32_t *>(b->stage) : nullptr;
+    p.prev = b->track ? b->prev : nullptr;
+    p.last_diff = b->track ? b->last_diff : nullptr;
+    for (int64_t done = 0; done < turns;) {
+        const int K = (int)std::min<int64_t>(kmax, turns - done);
+        p.t0 = b->turn;
+        BHIPCHK(b, launch_batch_board(K, b->W, b->R, b->nboards, p, b->stream));
+        if (history) {
+            BHIPCHK(b, hipMemcpy2DAsync(history + done, board_stride * sizeof(uint32_t), p.hist, (size_t)K * 4,
+                                        (size_t)K * 4, (size_t)b->nboards, hipMemcpyDeviceToHost, b->stream));
+            BHIPCHK(b, hipStreamSynchronize(b->stream));  // the next launch rewrites the stage
+        }
+        b->turn += K;
+        done += K;
+    }
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    return GOLHIP_OK;
+}
+
+int golhip_batch_alive_counts(golhip_batch_t b, uint32_t *out) {
+    if (!b) return GOLHIP_ERR_ARG;
+    if (!out) return bfail(b, GOLHIP_ERR_ARG, "out is null");
+    BHIPCHK(b, hipSetDevice(b->device));
+    uint32_t *d = reinterpret_cast<uint32_t *>(b->stage);  // stage_bytes >= 4 * nboards
+    BHIPCHK(b, launch_batch_popcount(b->boards, b->board_words, b->nboards, b->height, b->width, b->wd, d, b->stream));
+    BHIPCHK(b, hipMemcpyAsync(out, d, sizeof(uint32_t) * (size_t)b->nboards, hipMemcpyDeviceToHost, b->stream));
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    return GOLHIP_OK;
+}
+
+int golhip_batch_track_settle(golhip_batch_t b, int enable) {
+    if (!b) return GOLHIP_ERR_ARG;
+    if (!enable) {
+        b->track = false;
+        return GOLHIP_OK;
+    }
+    if (b->track) return GOLHIP_OK;
+    if (b->turn != 0)
+        return bfail(b, GOLHIP_ERR_STATE, "settle tracking starts at turn 0 (turn %lld): enable it after a load, "
+                     "before the first step", (long long)b->turn);
+    BHIPCHK(b, hipSetDevice(b->device));
+    if (!b->prev) BHIPCHK(b, hipMalloc(&b->prev, sizeof(uint32_t) * (size_t)b->board_words * (size_t)b->nboards));
+    if (!b->last_diff) BHIPCHK(b, hipMalloc(&b->last_diff, sizeof(unsigned long long) * (size_t)b->nboards));
+    BHIPCHK(b, hipMemsetAsync(b->last_diff, 0, sizeof(unsigned long long) * (size_t)b->nboards, b->stream));
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    b->track = true;
+    return GOLHIP_OK;
+}
+
+int golhip_batch_settled(golhip_batch_t b, int64_t *out) {
+    if (!b) return GOLHIP_ERR_ARG;
+    if (!out) return bfail(b, GOLHIP_ERR_ARG, "out is null");
+    if (!b->track) return bfail(b, GOLHIP_ERR_STATE, "settle tracking is off (golhip_batch_track_settle)");
+    BHIPCHK(b, hipSetDevice(b->device));
+    static_assert(sizeof(int64_t) == sizeof(unsigned long long), "last_diff is copied into out");
+    BHIPCHK(b, hipMemcpyAsync(out, b->last_diff, sizeof(int64_t) * (size_t)b->nboards, hipMemcpyDeviceToHost,
+                              b->stream));
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    // board(t) != board(t - 2) exactly for t in [2, D]: the settle turn is D + 1 (2 when nothing
+    // ever differed), known once that turn has been run
+    for (int i = 0; i < b->nboards; ++i) {
+        const int64_t t = std::max<int64_t>(out[i], 1) + 1;
+        out[i] = t <= b->turn ? t : -1;
+    }
+    return GOLHIP_OK;
+}
+
+int golhip_batch_turn(golhip_batch_t b, int64_t *out) {
+    if (!b || !out) return GOLHIP_ERR_ARG;
+    *out = b->turn;
+    return GOLHIP_OK;
+}
+
+}  // extern "C"

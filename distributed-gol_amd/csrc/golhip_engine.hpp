@@ -7,6 +7,7 @@
 //   engine_cells.hip    alive-cell lists and CellFlipped extraction, the per-turn flips ring
 //   engine_io.hip       host transfers (PGM bytes, uint64 words, random init) and checkpoints
 //   engine_view.hip     windowed access: a rectangle as bytes (out / in) and the density viewport
+//   engine_batch.hip    golhip_batch: many independent small tori on one device (its own handle type)
 // The tuning library adds tuning/engine_tuning.hip, which registers engine_hooks(); the production
 // library has no hooks (every hook pointer below stays null there).
 //
@@ -38,7 +39,7 @@
 
 namespace golhip {
 
-constexpr int kVersion = 104;  // 104: golhip_store_rect / _load_rect / _view_counts / _view
+constexpr int kVersion = 105;  // 105: golhip_batch_* (104: golhip_store_rect / _load_rect / _view_counts / _view)
 // Generations of per-turn counts finalized per launch (golhip_set_count_window changes it; at
 // least the graph length kGraphGens: tests shrink it to exercise flushes).
 constexpr int kCountWindowDefault = 4096;

@@ -282,6 +282,30 @@ constexpr int64_t kBoardAutoRows = 256;
 bool stencil_board_shape(int64_t height, int32_t wd, int *W, int *R);
 hipError_t launch_stencil_board(int K, int W, int R, const uint32_t *in_row0, uint32_t *out_row0,
                                 const StencilParams &p, unsigned long long *slots, hipStream_t s);
+// The batch kernel (batch_board.hip): nboards independent tori of that geometry, one workgroup
+// each, advanced K generations IN PLACE.  Board i is rows x wd words at boards + i * board_pitch.
+struct BatchParams {
+    uint32_t *boards;
+    int64_t board_pitch;  // words between boards: 4 W R wd
+    int32_t wd;           // words per torus row: 4, 8 or 16
+    int32_t width;        // cells per board row (counts take one copy of a replicated row)
+    // nullable: hist[i * K + g] = alive cells of board i after generation g of the launch
+    uint32_t *hist;
+    // settle tracking (both or neither): prev holds board(t0 - 1) of every board in the boards'
+    // layout (read unless t0 == 0, rewritten with board(t0 + K - 1)); last_diff[i] is raised to the
+    // last absolute turn t in (t0, t0 + K] with board_i(t) != board_i(t - 2)
+    uint32_t *prev;
+    unsigned long long *last_diff;
+    int64_t t0;  // turns completed before the launch
+};
+hipError_t launch_batch_board(int K, int W, int R, int nboards, const BatchParams &p, hipStream_t s);
+// init_random_rows for every board: board i from seeds ? seeds[i] (device memory) : seed0 + i.
+hipError_t launch_batch_init_random(uint32_t *boards, int64_t board_pitch, int64_t nboards, int64_t rows,
+                                    int64_t width, int32_t wd, const uint64_t *seeds, uint64_t seed0,
+                                    uint32_t density_q32, hipStream_t s);
+// out[i] = alive cells of board i.
+hipError_t launch_batch_popcount(const uint32_t *boards, int64_t board_pitch, int64_t nboards, int64_t rows,
+                                 int64_t width, int32_t wd, uint32_t *out, hipStream_t s);
 constexpr int kTileChunkWords = 62;
 // Words per column chunk of the level-split kernel (half-word halo for K <= 16).
 __host__ __device__ constexpr int split_chunk_words(int K) { return K <= 16 ? 63 : 62; }

@@ -57,6 +57,9 @@ EXPORTS = [
     "golhip_checkpoint_save", "golhip_checkpoint_load", "golhip_checkpoint_info",
     "golhip_parse_rule", "golhip_set_rule", "golhip_set_rule_masks", "golhip_get_rule",
     "golhip_store_rect", "golhip_load_rect", "golhip_view_counts", "golhip_view",
+    "golhip_batch_create", "golhip_batch_destroy", "golhip_batch_last_error", "golhip_batch_load_bytes",
+    "golhip_batch_store_bytes", "golhip_batch_init_random", "golhip_batch_step", "golhip_batch_alive_counts",
+    "golhip_batch_track_settle", "golhip_batch_settled", "golhip_batch_turn",
 ]
 
 
@@ -231,6 +234,17 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
         "golhip_view_counts": ([H, i64, i64, i64, i64, i32, ctypes.c_void_p], i32),
         "golhip_view": ([H, i64, i64, i64, i64, i32, ctypes.c_void_p, ctypes.c_size_t], i32),
         "golhip_launch_kind": ([H, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], i32),
+        "golhip_batch_create": ([i32, i32, i32, i32, ctypes.POINTER(H)], i32),
+        "golhip_batch_destroy": ([H], i32),
+        "golhip_batch_last_error": ([H], ctypes.c_char_p),
+        "golhip_batch_load_bytes": ([H, i32, i32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t], i32),
+        "golhip_batch_store_bytes": ([H, i32, i32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t], i32),
+        "golhip_batch_init_random": ([H, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32], i32),
+        "golhip_batch_step": ([H, i64, ctypes.c_void_p, ctypes.c_size_t], i32),
+        "golhip_batch_alive_counts": ([H, ctypes.c_void_p], i32),
+        "golhip_batch_track_settle": ([H, i32], i32),
+        "golhip_batch_settled": ([H, ctypes.c_void_p], i32),
+        "golhip_batch_turn": ([H, i64p], i32),
         "golhip_launch_kind_counts": ([H, i32, i32, ctypes.POINTER(ctypes.c_int),
                                        ctypes.POINTER(ctypes.c_int)], i32),
     }
@@ -775,3 +789,108 @@ class Engine:
         self._check(self._L.golhip_kernel_time(self._h, ctypes.byref(ms), ctypes.byref(launches),
                                                ctypes.byref(gens)))
         return ms.value, launches.value, gens.value
+
+
+class Batch:
+    """One golhip_batch handle: `nboards` independent tori of one small size on one device, all
+    advanced by one launch (one workgroup per board).  Sizes: widths whose lcm with 128 is 128, 256
+    or 512 (16, 64, 128, 256, 512, ...) and 4, 8, 16, ..., 512 rows.  Always B3/S23.  The batch has
+    one turn counter; any load() or init_random() sets it to 0 and clears the settle records."""
+
+    def __init__(self, width: int, height: int, nboards: int, device: int = 0, *,
+                 lib: ctypes.CDLL | None = None):
+        self._L = lib if lib is not None else load_library()
+        self._h = ctypes.c_void_p()
+        rc = self._L.golhip_batch_create(width, height, nboards, device, ctypes.byref(self._h))
+        if rc != OK:
+            why = self._L.golhip_batch_last_error(None).decode() or self._L.golhip_strerror(rc).decode()
+            raise GolHipError(rc, why)
+        self.width, self.height, self.nboards = int(width), int(height), int(nboards)
+
+    def _check(self, rc: int) -> int:
+        if rc != OK:
+            raise GolHipError(rc, self._L.golhip_batch_last_error(self._h).decode() or
+                              self._L.golhip_strerror(rc).decode())
+        return rc
+
+    def close(self):
+        if self._h:
+            self._L.golhip_batch_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def load(self, boards: np.ndarray, first: int = 0):
+        """Boards [first, first + n) from an (n, h, w) array of 0 / nonzero bytes (any strides whose
+        cells are contiguous within a row).  Resets the turn and the settle records."""
+        boards = np.asarray(boards, dtype=np.uint8)
+        assert boards.ndim == 3 and boards.shape[1:] == (self.height, self.width), boards.shape
+        if boards.strides[2] != 1 or boards.strides[1] < self.width or boards.strides[0] < 0:
+            boards = np.ascontiguousarray(boards)
+        self._check(self._L.golhip_batch_load_bytes(self._h, first, boards.shape[0], boards.ctypes.data,
+                                                    boards.strides[1], boards.strides[0]))
+
+    def init_random(self, seeds=None, seed0: int = 0, density_q32: int = DENSITY_HALF):
+        """Board i as Engine.init_random(seed_i, density_q32) of a single engine of this size,
+        seed_i = seeds[i] if seeds is given, else seed0 + i."""
+        ptr = None
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+            assert seeds.shape == (self.nboards,), seeds.shape
+            ptr = seeds.ctypes.data
+        self._check(self._L.golhip_batch_init_random(self._h, ptr, seed0, density_q32))
+
+    def store(self, first: int = 0, n: int | None = None, out: np.ndarray | None = None) -> np.ndarray:
+        """Boards [first, first + n) as 0 / 255 bytes, (n, h, w).  out: a uint8 (n, h, w) array (or
+        view: rows may be padded) to fill instead of a new one."""
+        n = self.nboards - first if n is None else n
+        if out is None:
+            out = np.empty((max(n, 0), self.height, self.width), dtype=np.uint8)
+        assert out.dtype == np.uint8 and out.shape == (n, self.height, self.width) and out.strides[2] == 1
+        self._check(self._L.golhip_batch_store_bytes(self._h, first, n, out.ctypes.data, out.strides[1],
+                                                     out.strides[0]))
+        return out
+
+    def step(self, turns: int, history: bool = False) -> np.ndarray | None:
+        """Advance every board `turns` generations.  history: return the (nboards, turns) uint32
+        alive counts after each turn of this call."""
+        if history:
+            out = np.zeros((self.nboards, max(turns, 0)), dtype=np.uint32)
+            if turns > 0:
+                self._check(self._L.golhip_batch_step(self._h, turns, out.ctypes.data, turns))
+            else:
+                self._check(self._L.golhip_batch_step(self._h, turns, None, 0))
+            return out
+        self._check(self._L.golhip_batch_step(self._h, turns, None, 0))
+        return None
+
+    def alive_counts(self) -> np.ndarray:
+        out = np.zeros(self.nboards, dtype=np.uint32)
+        self._check(self._L.golhip_batch_alive_counts(self._h, out.ctypes.data))
+        return out
+
+    def track_settle(self, on: bool = True):
+        """Settle tracking (golhip_batch_track_settle): enable it after a load, before the first step."""
+        self._check(self._L.golhip_batch_track_settle(self._h, int(on)))
+
+    def settled(self) -> np.ndarray:
+        """int64 per board: the smallest turn t >= 2 with board(t) == board(t - 2), -1 if not reached."""
+        out = np.zeros(self.nboards, dtype=np.int64)
+        self._check(self._L.golhip_batch_settled(self._h, out.ctypes.data))
+        return out
+
+    @property
+    def turn(self) -> int:
+        v = ctypes.c_int64()
+        self._check(self._L.golhip_batch_turn(self._h, ctypes.byref(v)))
+        return v.value

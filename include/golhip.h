@@ -401,6 +401,48 @@ int golhip_kernel_time(golhip_t h, double *total_ms, int64_t *launches, int64_t 
  * rank's time its neighbours and the transport cost it (the N > 1 bench line's per-rank data). */
 int golhip_edge_wait(golhip_t h, double *total_ms, int64_t *blocks);
 
+/* ---- batched small boards: many independent tori in one launch -------------------------------
+ * The reference runs one world per broker (broker/broker.go:157-180).  A soup search, a seed or
+ * density sweep or a census of what boards settle to runs thousands of small ones: a batch holds
+ * `nboards` independent tori of one size on one device and advances all of them per launch, one
+ * workgroup per board (gol_batch), with an optional per-board per-turn population history and
+ * on-device detection of the turn at which each board became periodic with period <= 2.
+ *   - Sizes: exactly those of the whole-board kernel (golhip_set_board_kernel): lcm(width, 128) of
+ *     128, 256 or 512 cells (the reference's 16/64/128/256/512 widths) and 4, 8, 16, ..., 512 rows.
+ *     Anything else, or nboards < 1, is GOLHIP_ERR_ARG with the offending value in
+ *     golhip_batch_last_error(NULL) and no handle; a failed allocation is GOLHIP_ERR_OOM and frees
+ *     what it had.  One device per handle: several GPUs are several handles.
+ *   - The rule is B3/S23 (no rule setter).
+ *   - Board i of a load or store sits at cells + (i - first) * board_stride + y * row_stride; input
+ *     0 / nonzero, output 0 / 255.  No call but create and the first golhip_batch_track_settle(b, 1)
+ *     allocates device memory: bytes, seeds, counts and history go through a transfer stage in chunks.
+ *   - A batch has ONE turn counter.  Any golhip_batch_load_bytes, even of part of the batch, and any
+ *     golhip_batch_init_random set it to 0 and clear every settle record: a batch is filled, then run.
+ *   - golhip_batch_init_random: board i is bit for bit what golhip_init_random(seed_i, density_q32)
+ *     gives a single engine of that size, seed_i = seeds ? seeds[i] : seed0 + i (width % 64 == 0).
+ *   - golhip_batch_step runs `turns` generations of every board and returns when they are done.
+ *     history (nullable): history[i * board_stride + j] = alive cells of board i after the j-th turn
+ *     of this call (board_stride >= turns, in uint32 units).  turns == 0 is a no-op.
+ *   - Settling: with tracking on, settled[i] is the smallest absolute turn t >= 2 with
+ *     board_i(t) == board_i(t - 2), or -1 while no such turn has been run; once set it never changes,
+ *     and it does not depend on how the turns were cut into calls.  Tracking starts at turn 0:
+ *     enabling it after turns have run is GOLHIP_ERR_STATE, golhip_batch_settled without it too. */
+typedef struct golhip_batch *golhip_batch_t;
+int golhip_batch_create(int width, int height, int nboards, int device, golhip_batch_t *out);
+int golhip_batch_destroy(golhip_batch_t b);
+const char *golhip_batch_last_error(golhip_batch_t b); /* NULL: why the last create failed (this thread) */
+int golhip_batch_load_bytes(golhip_batch_t b, int first, int n, const uint8_t *cells, size_t row_stride,
+                            size_t board_stride);
+int golhip_batch_store_bytes(golhip_batch_t b, int first, int n, uint8_t *out, size_t row_stride,
+                             size_t board_stride);
+int golhip_batch_init_random(golhip_batch_t b, const uint64_t *seeds /* nboards, or NULL */, uint64_t seed0,
+                             uint32_t density_q32);
+int golhip_batch_step(golhip_batch_t b, int64_t turns, uint32_t *history, size_t board_stride);
+int golhip_batch_alive_counts(golhip_batch_t b, uint32_t *out /* nboards */);
+int golhip_batch_track_settle(golhip_batch_t b, int enable);
+int golhip_batch_settled(golhip_batch_t b, int64_t *out /* nboards */);
+int golhip_batch_turn(golhip_batch_t b, int64_t *out);
+
 #ifdef __cplusplus
 }
 #endif

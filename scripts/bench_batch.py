@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""Cell updates per second of golhip.Batch (many small tori, one gol_batch launch) on the GPU.
+
+For 64 x 64, 128 x 64 and 512 x 512 boards and B in {1, 256, 4096, 65536} boards per batch (where
+the boards and their settle copy fit in 16 GiB), calls of 1000 turns in three modes:
+
+  plain          Batch.step(1000)
+  history        Batch.step(1000, history=True): every board's alive count after every turn, in a
+                 fresh (B, 1000) uint32 host array per call
+  history+settle the same with Batch.track_settle() on; its cost is reported as the ratio of its
+                 call time to the history mode's
+
+Every figure is a host clock around a whole call, which ends in a device synchronise: 2 warm calls,
+then --calls (>= 7) timed ones, the median; rate = B * width * height * 1000 / median.
+
+The yardstick is the only route there was before the batch, measured in the same process: ONE
+Engine of that size with set_board_kernel(1), and per board load() + step(1000) + store() (with
+counts=True beside the history modes), timed over --yardstick-boards boards; a batch of B boards is
+set beside B times its median.  --ceiling-json: the JSON line of a bench.py run of the same
+session (its "value", GCUPS at 65536^2), quoted beside the rates.
+
+One JSON line on stdout; --out also writes it to a file.  There is no CPU fallback: without a GPU
+the script fails.
+"""
+import argparse
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT / "distributed-gol_amd"))
+import golhip  # noqa: E402
+
+TURNS = 1000
+SHAPES = [(64, 64), (128, 64), (512, 512)]
+BATCHES = [1, 256, 4096, 65536]
+
+
+def median_s(fn, warm, calls):
+    for _ in range(warm):
+        fn()
+    ts = []
+    for _ in range(calls):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return statistics.median(ts), min(ts)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=7)
+    ap.add_argument("--yardstick-boards", type=int, default=32)
+    ap.add_argument("--ceiling-json", type=Path)
+    ap.add_argument("--out", type=Path)
+    a = ap.parse_args()
+    assert a.calls >= 7
+    res = {"bench": "batch", "version": golhip.load_library().golhip_version(), "turns": TURNS,
+           "calls": a.calls, "shapes": []}
+    if a.ceiling_json:
+        line = [ln for ln in a.ceiling_json.read_text().splitlines() if ln.startswith("{")][-1]
+        res["ceiling_65536sq_gcups"] = json.loads(line)["value"]
+    budget = 16 << 30  # bytes of boards plus their settle copy a batch may take here
+    for w, h in SHAPES:
+        cells = w * h
+        entry = {"width": w, "height": h, "batches": []}
+        # the yardstick: one engine, board after board
+        rng = np.random.default_rng(1)
+        board = (rng.random((h, w)) < 0.5).astype(np.uint8) * 255
+        with golhip.Engine(w, h, k=16) as e:
+            e.set_board_kernel(1)
+            assert e.launch_kind(16)[0] == "board"
+
+            def one(counts):
+                e.load(board)
+                e.step(TURNS, counts=counts)
+                if not counts:
+                    e.sync()
+                e.store()
+
+            y = {}
+            for name, counts in (("plain", False), ("counts", True)):
+                med, best = median_s(lambda: one(counts), 3, a.yardstick_boards)
+                y[name] = {"per_board_ms_median": round(med * 1e3, 4), "per_board_ms_min": round(best * 1e3, 4),
+                           "gcups": round(cells * TURNS / med / 1e9, 3)}
+        entry["engine_loop"] = y
+        for B in BATCHES:
+            words = h * max(w, 128) // 32 * 4  # bytes of one packed board
+            if B * words * 2 > budget:
+                entry["batches"].append({"boards": B, "skipped": "over 16 GiB of boards"})
+                continue
+            row = {"boards": B}
+            for mode in ("plain", "history", "history+settle"):
+                with golhip.Batch(w, h, B) as b:
+                    b.init_random(seed0=1)
+                    if mode == "history+settle":
+                        b.track_settle()
+                    hist = mode != "plain"
+                    med, best = median_s(lambda: b.step(TURNS, history=hist), 2, a.calls)
+                loop = y["plain" if mode == "plain" else "counts"]["per_board_ms_median"] * 1e-3 * B
+                row[mode] = {"call_ms_median": round(med * 1e3, 3), "call_ms_min": round(best * 1e3, 3),
+                             "per_board_us": round(med / B * 1e6, 3),
+                             "gcups": round(B * cells * TURNS / med / 1e9, 2),
+                             "engine_loop_ms": round(loop * 1e3, 3),
+                             "speedup_over_engine_loop": round(loop / med, 2)}
+            row["settle_cost_ratio"] = round(row["history+settle"]["call_ms_median"] / row["history"]["call_ms_median"], 3)
+            entry["batches"].append(row)
+            print(json.dumps({"shape": [w, h], **row}), file=sys.stderr, flush=True)
+        res["shapes"].append(entry)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        a.out.parent.mkdir(parents=True, exist_ok=True)
+        a.out.write_text(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
