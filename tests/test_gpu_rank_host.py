@@ -41,7 +41,7 @@ def _free_port():
 SCHEDULE = [1, 7, 20, 33, 16, 3]  # K = 1 launches, tail plans, bulk depths, a short call
 
 
-def _worker(rank, world, port, width, height, k, out_dir, transport="host"):
+def _worker(rank, world, port, width, height, k, out_dir, transport="host", rule=None):
     for p in (str(ROOT / "oracle"), str(PKG)):
         if p not in sys.path:
             sys.path.insert(0, p)
@@ -64,12 +64,13 @@ def _worker(rank, world, port, width, height, k, out_dir, transport="host"):
         nid = obj[0]
     res = {}
     with golhip.Engine(width, height, k=k, rank=rank, world_size=world, device=0,
-                       host_comm=comm, nccl_id=nid) as e:
+                       host_comm=comm, nccl_id=nid, rule=rule) as e:
         y0, rows = e.info.y0, e.info.rows
         assert (y0, rows) == golhip.strip_bounds(height, world, rank)
         e.load_words(oracle.init_random(width, height, seed=11)[y0:y0 + rows])
         counts = [e.step(n, counts=True) for n in SCHEDULE]
         res["counts"] = np.concatenate(counts)
+        res["rule_kernel"] = np.array([e.launch_kind(k, counts=True)[0] == "rule"])
         res["alive"] = np.array([e.alive_count()])
         res["words"] = e.store_words()
         res["cells"] = e.alive_cells()
@@ -142,6 +143,55 @@ def test_rank_engine_matches_oracle(tmp_path, oracle, world, width, height, k, t
         ex = [int(x["exchanges"][0]) for x in r]
         assert len(set(ex)) == 1 and ex[0] >= len(SCHEDULE) + 5
         assert all(np.array_equal(x["reduced"], r[0]["reduced"]) for x in r)
+
+
+@pytest.mark.parametrize("transport", ["rccl", "host"])
+def test_rank_engine_under_a_rule_matches_numpy(tmp_path, oracle, transport):
+    """The same worker at world 2 under AntiLife (B0123478/S01234678: a B0 rule in the table form)
+    on 576 x 101 at k = 8 -- the replicated width, strips of 50 / 51 rows, so every 8-deep launch is
+    gol_rule's interior beside its two boundary bands, with "rccl" the interior enqueued before the
+    exchange; rows outside a strip are clamped, and under B0 what is computed from them is alive.
+    Every rank's strip, every count, the alive cells and the ring's flips against the numpy stepper
+    of tests/test_gpu_rules.py, and against the oracle through the complement identity."""
+    from test_gpu_rules import ANTILIFE, flips_of, np_run
+
+    world, width, height, k = 2, 576, 101, 8
+    mp.start_processes(_worker, args=(world, _free_port(), width, height, k, str(tmp_path), transport, ANTILIFE),
+                       nprocs=world, join=True, start_method="spawn")
+    r = [dict(np.load(tmp_path / f"rank{i}.npz")) for i in range(world)]
+    words = oracle.init_random(width, height, seed=11)
+    cells = (oracle.unpack(words, width) != 0).astype(np.uint8)
+    turns = sum(SCHEDULE)
+    gens, exp = np_run(cells, ANTILIFE, turns + 15)
+    for t in (turns, turns + 10, turns + 15):  # liveness of the reference, before any comparison
+        assert 0 < exp[t - 1] < width * height
+        assert 100 * np.count_nonzero(gens[t] != gens[t - 1]) >= width * height
+    life = ~words  # 576 = 9 whole words: no padding bits to complement
+    life_counts = width * height - np.concatenate([oracle.packed_run_words(life, n) for n in (turns, 10, 5)])
+    assert np.array_equal(exp, life_counts)
+    assert np.array_equal((oracle.unpack(life, width) == 0).astype(np.uint8), gens[turns + 15])
+    board = lambda key: (oracle.unpack(np.concatenate([x[key] for x in r]), width) != 0).astype(np.uint8)  # noqa: E731
+    for i in range(world):
+        assert bool(r[i]["rule_kernel"][0])
+        assert np.array_equal(r[i]["counts"].astype(np.int64), exp[:turns]), i
+        assert int(r[i]["alive"][0]) == int(exp[turns - 1])
+        assert np.array_equal(r[i]["counts_fixed"].astype(np.int64), exp[turns:turns + 10]), i
+        assert np.array_equal(r[i]["flips_alive"].astype(np.int64), exp[turns + 10:]), i
+    assert np.array_equal(board("words"), gens[turns])
+    ys, xs = np.nonzero(gens[turns])
+    assert np.array_equal(np.concatenate([x["cells"] for x in r]), np.stack([xs, ys], axis=1).astype(np.int32))
+    off = [0] * world
+    for t in range(5):
+        got = []
+        for i in range(world):
+            n = int(r[i]["flips_n"][t])
+            got.append(r[i]["flips"][off[i]:off[i] + n])
+            off[i] += n
+        assert np.array_equal(np.concatenate(got), flips_of(gens[turns + 10 + t], gens[turns + 11 + t])), t
+    assert np.array_equal(board("words_end"), gens[turns + 15])
+    if transport == "host":
+        ex = [int(x["exchanges"][0]) for x in r]
+        assert len(set(ex)) == 1 and ex[0] >= len(SCHEDULE) + 5
 
 
 @pytest.mark.timeout(700)

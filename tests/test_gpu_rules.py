@@ -6,7 +6,10 @@ strips, multi-strip handles, per-turn counts, the flips ring, flip tracking and 
 The oracle is B3/S23 only, so the reference is the numpy stepper below (eight rolls summed, then
 where(alive, survive >> n & 1, birth >> n & 1)); everything is bit-exact.  tests/test_rules_cpu.py
 checks that stepper against the oracle at B3/S23, and the kernel's algebra without a GPU.
-Rank mode over RCCL shares the strips' launch path and halo mode and has no rule test of its own.
+tests/test_gpu_rules_matrix.py runs every functor at every depth with and without counts and flips,
+boards down to one row, strips that take the K = 8 interior + boundary split, rank mode as the RCCL
+ring of one, rule changes at depth and the checkpoint; tests/test_gpu_rank_host.py runs two real
+ranks under AntiLife over both transports.
 """
 import functools
 import subprocess

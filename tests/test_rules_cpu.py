@@ -206,3 +206,19 @@ def test_numpy_stepper_agrees_with_the_oracle_for_life(oracle):
         cur = np.where(cur == 1, (0x00C >> n) & 1, (0x008 >> n) & 1).astype(np.uint8)
     got, _ = oracle.packed_run(board * 255, 5)
     assert np.array_equal(cur * 255, got)
+
+
+@pytest.mark.parametrize("w,h", [(128, 1), (128, 2), (128, 3), (48, 5), (3968, 9)])
+def test_numpy_stepper_agrees_with_the_oracle_on_degenerate_heights(oracle, w, h):
+    """np_step / np_run of tests/test_gpu_rules.py at B3/S23 against the oracle, every one of 10
+    turns and its count, on boards of 1, 2 and 3 rows (the three neighbour rows coincide), the
+    replicated 48-wide torus and the two-full-chunk width: the shapes the GPU rule tests lean on."""
+    from test_gpu_rules import np_run, random_cells
+
+    board = random_cells(w, h, w * 31 + h)
+    gens, counts = np_run(board, (0x008, 0x00C), 10)
+    assert 0 < counts[0] < w * h  # the first turn is not trivial
+    for t in range(1, 11):
+        got, got_counts = oracle.packed_run(board * 255, t)
+        assert np.array_equal(gens[t] * 255, got), t
+        assert np.array_equal(counts[:t], got_counts.astype(np.int64)), t
