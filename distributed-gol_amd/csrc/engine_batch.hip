@@ -6,18 +6,27 @@
 // -- the sizes of the whole-board kernel, stencil_board_shape: 4, 8 or 16 torus words wide, 4 W R
 // rows -- back to back in one allocation, board i at boards + i * height * wd words in the packed
 // layout of a single engine of that size, and advances all of them with one gol_batch launch per
-// <= kBoardMaxK generations (batch_board.hip: one workgroup per board, in place).  Always B3/S23.
+// <= kBoardMaxK generations (batch_board.hip: one workgroup per board, in place).
 //
-// Device memory is allocated at create (the boards, the per-board counters, the transfer stage) and
-// by the first golhip_batch_track_settle(b, 1) (board(t - 1) of every board); no other call
-// allocates.  Bytes in and out, the seeds of init_random, per-board counts and the per-turn
-// history all pass through the stage in chunks.
+// The rule.  A batch starts at B3/S23 and a uniform B3/S23 always launches gol_batch.  Any other
+// life-like rule -- one for all boards (golhip_batch_set_rule / _set_rule_masks) or one per board
+// (golhip_batch_set_rules) -- launches gol_batch_rule (batch_rule.hpp): constant-folded for a
+// uniform catalogue rule, the table form for every other uniform rule and for per-board rules
+// whatever they are.  golhip_batch_kernel reports which.  The settle record is the record of one
+// rule, so with tracking on the rule changes at turn 0 only.
+//
+// Device memory is allocated at create (the boards, the per-board counters, the transfer stage), by
+// the first golhip_batch_track_settle(b, 1) (board(t - 1) of every board) and by the first
+// golhip_batch_set_rules (the per-board rule pairs); no other call allocates.  Bytes in and out,
+// the seeds of init_random, per-board rules and counts and the per-turn history all pass through
+// the stage in chunks.
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "golhip_engine.hpp"
 
@@ -35,6 +44,10 @@ struct golhip_batch {
     int64_t stage_bytes = 0;
     bool track = false;
     int64_t turn = 0;
+    golhip::RuleMasks rule{golhip::kLifeBirth, golhip::kLifeSurvive};  // the uniform rule
+    bool per_board = false;              // the boards run `rules`, not `rule`
+    uint32_t *rules = nullptr;           // device: nboards (birth, survive) pairs
+    std::vector<uint32_t> rules_host;    // the same pairs, for golhip_batch_get_rules
     std::string err;
 };
 
@@ -69,8 +82,9 @@ void batch_free(golhip_batch_t b) {
     if (b->prev) (void)hipFree(b->prev);
     if (b->last_diff) (void)hipFree(b->last_diff);
     if (b->stage) (void)hipFree(b->stage);
+    if (b->rules) (void)hipFree(b->rules);
     if (b->stream) (void)hipStreamDestroy(b->stream);
-    b->boards = b->prev = nullptr;
+    b->boards = b->prev = b->rules = nullptr;
     b->last_diff = nullptr;
     b->stage = nullptr;
     b->stream = nullptr;
@@ -143,6 +157,22 @@ int transfer(golhip_batch_t b, int first, int n, uint8_t *host, size_t row_strid
         if (to_device) BHIPCHK(b, launch_pack(b->stage, nr, W, b->wd, dev, b->wd, b->stream));
         BHIPCHK(b, hipStreamSynchronize(b->stream));
     }
+    return GOLHIP_OK;
+}
+
+// What the next step launches: 0 gol_batch (uniform B3/S23), 1 gol_batch_rule constant-folded, 2 its
+// table form, 3 the table form with per-board rules.
+int kernel_form(const golhip_batch *b) {
+    if (b->per_board) return 3;
+    if (b->rule.birth == kLifeBirth && b->rule.survive == kLifeSurvive) return 0;
+    return rule_catalogued(b->rule.birth, b->rule.survive) ? 1 : 2;
+}
+
+// The settle record (last_diff, prev) describes the boards under one rule.
+int rule_change_allowed(golhip_batch_t b) {
+    if (b->track && b->turn > 0)
+        return bfail(b, GOLHIP_ERR_STATE, "settle tracking is on at turn %lld: the settle record holds under one rule, "
+                     "change the rule at turn 0 (after a load)", (long long)b->turn);
     return GOLHIP_OK;
 }
 
@@ -255,10 +285,16 @@ int golhip_batch_step(golhip_batch_t b, int64_t turns, uint32_t *history, size_t
     p.hist = history ? reinterpret_cast<uint32_t *>(b->stage) : nullptr;
     p.prev = b->track ? b->prev : nullptr;
     p.last_diff = b->track ? b->last_diff : nullptr;
+    const int form = kernel_form(b);
     for (int64_t done = 0; done < turns;) {
         const int K = (int)std::min<int64_t>(kmax, turns - done);
         p.t0 = b->turn;
-        BHIPCHK(b, launch_batch_board(K, b->W, b->R, b->nboards, p, b->stream));
+        if (form == 0) {
+            BHIPCHK(b, launch_batch_board(K, b->W, b->R, b->nboards, p, b->stream));
+        } else {  // a missing kernel is an error, never gol_batch
+            const BatchRuleParams rp{p, b->rule, b->per_board ? b->rules : nullptr};
+            BHIPCHK(b, launch_batch_rule(K, b->W, b->R, b->nboards, rp, b->stream));
+        }
         if (history) {
             BHIPCHK(b, hipMemcpy2DAsync(history + done, board_stride * sizeof(uint32_t), p.hist, (size_t)K * 4,
                                         (size_t)K * 4, (size_t)b->nboards, hipMemcpyDeviceToHost, b->stream));
@@ -322,6 +358,88 @@ int golhip_batch_settled(golhip_batch_t b, int64_t *out) {
 int golhip_batch_turn(golhip_batch_t b, int64_t *out) {
     if (!b || !out) return GOLHIP_ERR_ARG;
     *out = b->turn;
+    return GOLHIP_OK;
+}
+
+int golhip_batch_set_rule_masks(golhip_batch_t b, uint32_t birth, uint32_t survive) {
+    if (!b) return GOLHIP_ERR_ARG;
+    if ((birth | survive) & ~kRuleMaskBits)
+        return bfail(b, GOLHIP_ERR_ARG, "rule masks birth=0x%x survive=0x%x: bits above 8 (a cell has 8 neighbours)",
+                     birth, survive);
+    if (!b->per_board && birth == b->rule.birth && survive == b->rule.survive) return GOLHIP_OK;
+    const int rc = rule_change_allowed(b);
+    if (rc) return rc;
+    b->rule.birth = birth;
+    b->rule.survive = survive;
+    b->per_board = false;
+    return GOLHIP_OK;
+}
+
+int golhip_batch_set_rule(golhip_batch_t b, const char *rule) {
+    if (!b) return GOLHIP_ERR_ARG;
+    uint32_t birth = 0, survive = 0;
+    if (golhip_parse_rule(rule, &birth, &survive) != GOLHIP_OK) return bfail(b, GOLHIP_ERR_ARG, "%s", g_create_error.c_str());
+    return golhip_batch_set_rule_masks(b, birth, survive);
+}
+
+int golhip_batch_get_rule(golhip_batch_t b, uint32_t *birth, uint32_t *survive) {
+    if (!b || !birth || !survive) return GOLHIP_ERR_ARG;
+    if (b->per_board)
+        return bfail(b, GOLHIP_ERR_STATE, "the boards have rules of their own (golhip_batch_get_rules)");
+    *birth = b->rule.birth;
+    *survive = b->rule.survive;
+    return GOLHIP_OK;
+}
+
+int golhip_batch_set_rules(golhip_batch_t b, const uint32_t *birth, const uint32_t *survive) {
+    if (!b) return GOLHIP_ERR_ARG;
+    if (!birth != !survive) return bfail(b, GOLHIP_ERR_ARG, "birth and survive: both arrays, or both null");
+    if (birth) {
+        for (int i = 0; i < b->nboards; ++i) {
+            if ((birth[i] | survive[i]) & ~kRuleMaskBits)
+                return bfail(b, GOLHIP_ERR_ARG, "board %d: rule masks birth=0x%x survive=0x%x: bits above 8 (a cell "
+                             "has 8 neighbours)", i, birth[i], survive[i]);
+        }
+    }
+    if (!birth && !b->per_board) return GOLHIP_OK;
+    int rc = rule_change_allowed(b);
+    if (rc) return rc;
+    if (!birth) {  // back to the uniform rule
+        b->per_board = false;
+        return GOLHIP_OK;
+    }
+    BHIPCHK(b, hipSetDevice(b->device));
+    const size_t n = (size_t)b->nboards;
+    if (!b->rules) BHIPCHK(b, hipMalloc(&b->rules, 2 * sizeof(uint32_t) * n));
+    std::vector<uint32_t> pairs(2 * n);
+    for (size_t i = 0; i < n; ++i) pairs[2 * i] = birth[i], pairs[2 * i + 1] = survive[i];
+    // through the stage, as many pairs at a time as it holds (>= 4 nboards bytes: at most two chunks)
+    const size_t cp = std::max<size_t>(1, (size_t)b->stage_bytes / (2 * sizeof(uint32_t)));
+    b->per_board = false;  // a failed upload leaves the uniform rule
+    for (size_t i = 0; i < n; i += cp) {
+        const size_t bytes = 2 * sizeof(uint32_t) * std::min(cp, n - i);
+        BHIPCHK(b, hipMemcpyAsync(b->stage, pairs.data() + 2 * i, bytes, hipMemcpyHostToDevice, b->stream));
+        BHIPCHK(b, hipMemcpyAsync(b->rules + 2 * i, b->stage, bytes, hipMemcpyDeviceToDevice, b->stream));
+        BHIPCHK(b, hipStreamSynchronize(b->stream));
+    }
+    b->rules_host.swap(pairs);
+    b->per_board = true;
+    return GOLHIP_OK;
+}
+
+int golhip_batch_get_rules(golhip_batch_t b, uint32_t *birth, uint32_t *survive) {
+    if (!b) return GOLHIP_ERR_ARG;
+    if (!birth || !survive) return bfail(b, GOLHIP_ERR_ARG, "out is null");
+    for (int i = 0; i < b->nboards; ++i) {
+        birth[i] = b->per_board ? b->rules_host[2 * (size_t)i] : b->rule.birth;
+        survive[i] = b->per_board ? b->rules_host[2 * (size_t)i + 1] : b->rule.survive;
+    }
+    return GOLHIP_OK;
+}
+
+int golhip_batch_kernel(golhip_batch_t b, int *form) {
+    if (!b || !form) return GOLHIP_ERR_ARG;
+    *form = kernel_form(b);
     return GOLHIP_OK;
 }
 

@@ -299,6 +299,22 @@ struct BatchParams {
     int64_t t0;  // turns completed before the launch
 };
 hipError_t launch_batch_board(int K, int W, int R, int nboards, const BatchParams &p, hipStream_t s);
+// The batch kernel for life-like rules (gol_batch_rule, batch_rule.hpp; one translation unit per
+// functor, batch_rule_*.hip): gol_batch's contract (b) under `rule`, or, with rules != null, board i
+// under its own pair rules[2 i] = birth, rules[2 i + 1] = survive (device memory, nboards pairs).
+// A uniform catalogue rule runs its constant-folded kernel; every other uniform rule and every
+// launch with per-board rules runs the table form.  B3/S23 as a uniform rule is launch_batch_board's.
+struct BatchRuleParams {
+    BatchParams b;
+    RuleMasks rule;
+    const uint32_t *rules;
+};
+hipError_t launch_batch_rule(int K, int W, int R, int nboards, const BatchRuleParams &rp, hipStream_t s);
+#define GOLHIP_X(B, S)                                                                                    \
+    hipError_t launch_batch_rule_##B##_##S(int K, int W, int R, int nboards, const BatchRuleParams &rp, \
+                                           hipStream_t s);
+GOLHIP_RULE_CATALOGUE(GOLHIP_X)
+#undef GOLHIP_X
 // init_random_rows for every board: board i from seeds ? seeds[i] (device memory) : seed0 + i.
 hipError_t launch_batch_init_random(uint32_t *boards, int64_t board_pitch, int64_t nboards, int64_t rows,
                                     int64_t width, int32_t wd, const uint64_t *seeds, uint64_t seed0,

@@ -60,6 +60,8 @@ EXPORTS = [
     "golhip_batch_create", "golhip_batch_destroy", "golhip_batch_last_error", "golhip_batch_load_bytes",
     "golhip_batch_store_bytes", "golhip_batch_init_random", "golhip_batch_step", "golhip_batch_alive_counts",
     "golhip_batch_track_settle", "golhip_batch_settled", "golhip_batch_turn",
+    "golhip_batch_set_rule", "golhip_batch_set_rule_masks", "golhip_batch_get_rule", "golhip_batch_set_rules",
+    "golhip_batch_get_rules", "golhip_batch_kernel",
 ]
 
 
@@ -245,6 +247,12 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
         "golhip_batch_track_settle": ([H, i32], i32),
         "golhip_batch_settled": ([H, ctypes.c_void_p], i32),
         "golhip_batch_turn": ([H, i64p], i32),
+        "golhip_batch_set_rule": ([H, ctypes.c_char_p], i32),
+        "golhip_batch_set_rule_masks": ([H, ctypes.c_uint32, ctypes.c_uint32], i32),
+        "golhip_batch_get_rule": ([H, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)], i32),
+        "golhip_batch_set_rules": ([H, ctypes.c_void_p, ctypes.c_void_p], i32),
+        "golhip_batch_get_rules": ([H, ctypes.c_void_p, ctypes.c_void_p], i32),
+        "golhip_batch_kernel": ([H, ctypes.POINTER(i32)], i32),
         "golhip_launch_kind_counts": ([H, i32, i32, ctypes.POINTER(ctypes.c_int),
                                        ctypes.POINTER(ctypes.c_int)], i32),
     }
@@ -794,18 +802,55 @@ class Engine:
 class Batch:
     """One golhip_batch handle: `nboards` independent tori of one small size on one device, all
     advanced by one launch (one workgroup per board).  Sizes: widths whose lcm with 128 is 128, 256
-    or 512 (16, 64, 128, 256, 512, ...) and 4, 8, 16, ..., 512 rows.  Always B3/S23.  The batch has
-    one turn counter; any load() or init_random() sets it to 0 and clears the settle records."""
+    or 512 (16, 64, 128, 256, 512, ...) and 4, 8, 16, ..., 512 rows.  The batch has one turn counter;
+    any load() or init_random() sets it to 0 and clears the settle records.
+
+    The rule is B3/S23 unless `rule` ("B36/S23" or (birth, survive) masks: one life-like rule for all
+    boards) or `rules` (one per board) is given, or set later with set_rule() / set_rules().  A
+    uniform B3/S23 runs gol_batch; any other rule runs gol_batch_rule, constant-folded for a uniform
+    catalogue rule, in the table form otherwise -- per-board rules always (kernel_form).  Rule texts
+    and the length of `rules` are checked before the handle is created: a bad one raises
+    GolHipError(ERR_ARG) naming it, without touching a device."""
 
     def __init__(self, width: int, height: int, nboards: int, device: int = 0, *,
-                 lib: ctypes.CDLL | None = None):
+                 rule: str | tuple[int, int] | None = None, rules=None, lib: ctypes.CDLL | None = None):
         self._L = lib if lib is not None else load_library()
         self._h = ctypes.c_void_p()
+        masks = None if rule is None else self._masks_of(rule)
+        pairs = None if rules is None else self._pairs_of(rules, int(nboards))
         rc = self._L.golhip_batch_create(width, height, nboards, device, ctypes.byref(self._h))
         if rc != OK:
             why = self._L.golhip_batch_last_error(None).decode() or self._L.golhip_strerror(rc).decode()
             raise GolHipError(rc, why)
         self.width, self.height, self.nboards = int(width), int(height), int(nboards)
+        if masks is not None:
+            self.set_rule(masks)
+        if pairs is not None:
+            self.set_rules(pairs)
+
+    def _masks_of(self, rule, where: str = "") -> tuple[int, int]:
+        """(birth, survive) of a rule text or a pair of masks; GolHipError(ERR_ARG) naming a bad one."""
+        try:
+            if isinstance(rule, (str, bytes)):
+                return parse_rule(rule, self._L)
+            birth, survive = (int(v) for v in rule)
+            if birth < 0 or survive < 0 or (birth | survive) & ~0x1FF:
+                raise GolHipError(ERR_ARG, f"rule masks birth={birth:#x} survive={survive:#x}: bits above 8 "
+                                           "(a cell has 8 neighbours)")
+            return birth, survive
+        except GolHipError as e:
+            raise GolHipError(e.code, where + str(e).split(": ", 1)[1]) if where else e
+        except (TypeError, ValueError):
+            raise GolHipError(ERR_ARG, f"{where}rule {rule!r}: a text like \"B36/S23\" or (birth, survive) masks")
+
+    def _pairs_of(self, rules, nboards: int) -> np.ndarray:
+        """An (nboards, 2) uint32 array of masks from a sequence of rule texts or (birth, survive) pairs,
+        or an (nboards, 2) integer array."""
+        n = len(rules)
+        if n != nboards:
+            raise GolHipError(ERR_ARG, f"rules: {n} rules for {nboards} boards")
+        return np.array([self._masks_of(r, f"rules[{i}]: ") for i, r in enumerate(rules)],
+                        dtype=np.uint32).reshape(nboards, 2)
 
     def _check(self, rc: int) -> int:
         if rc != OK:
@@ -893,4 +938,53 @@ class Batch:
     def turn(self) -> int:
         v = ctypes.c_int64()
         self._check(self._L.golhip_batch_turn(self._h, ctypes.byref(v)))
+        return v.value
+
+    # -- the rule
+    def set_rule(self, rule: str | tuple[int, int]):
+        """One rule for all boards (golhip_batch_set_rule): "B36/S23" or (birth, survive) masks.  Keeps
+        the boards, the turn and the settle switch; with settle tracking on, only at turn 0."""
+        if isinstance(rule, (str, bytes)):
+            self._check(self._L.golhip_batch_set_rule(self._h, rule.encode() if isinstance(rule, str) else rule))
+        else:
+            birth, survive = self._masks_of(rule)
+            self._check(self._L.golhip_batch_set_rule_masks(self._h, birth, survive))
+
+    def set_rules(self, rules):
+        """One rule per board (golhip_batch_set_rules): a sequence of nboards rule texts or (birth,
+        survive) pairs, or an (nboards, 2) integer array; None: back to the uniform rule.  Per-board
+        rules always run the table form of the kernel (kernel_form == 3)."""
+        if rules is None:
+            self._check(self._L.golhip_batch_set_rules(self._h, None, None))
+            return
+        pairs = self._pairs_of(rules, self.nboards)
+        birth, survive = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+        self._check(self._L.golhip_batch_set_rules(self._h, birth.ctypes.data, survive.ctypes.data))
+
+    @property
+    def rule_masks(self) -> tuple[int, int]:
+        """The uniform rule's (birth, survive); GolHipError(ERR_STATE) while per-board rules are set."""
+        b, s = ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(self._L.golhip_batch_get_rule(self._h, ctypes.byref(b), ctypes.byref(s)))
+        return b.value, s.value
+
+    @property
+    def rule(self) -> str:
+        """The uniform rule in canonical form, e.g. "B36/S23"."""
+        return rule_string(*self.rule_masks)
+
+    @property
+    def rules(self) -> np.ndarray:
+        """(nboards, 2) uint32: every board's (birth, survive), the uniform rule repeated when no
+        per-board rules are set."""
+        birth, survive = np.zeros(self.nboards, dtype=np.uint32), np.zeros(self.nboards, dtype=np.uint32)
+        self._check(self._L.golhip_batch_get_rules(self._h, birth.ctypes.data, survive.ctypes.data))
+        return np.stack([birth, survive], axis=1)
+
+    @property
+    def kernel_form(self) -> int:
+        """What the next step launches: 0 gol_batch (B3/S23), 1 gol_batch_rule constant-folded, 2 its
+        table form, 3 the table form with per-board rules."""
+        v = ctypes.c_int32()
+        self._check(self._L.golhip_batch_kernel(self._h, ctypes.byref(v)))
         return v.value

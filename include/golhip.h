@@ -412,10 +412,11 @@ int golhip_edge_wait(golhip_t h, double *total_ms, int64_t *blocks);
  *     Anything else, or nboards < 1, is GOLHIP_ERR_ARG with the offending value in
  *     golhip_batch_last_error(NULL) and no handle; a failed allocation is GOLHIP_ERR_OOM and frees
  *     what it had.  One device per handle: several GPUs are several handles.
- *   - The rule is B3/S23 (no rule setter).
+ *   - The rule is B3/S23 unless one is set: golhip_batch_set_rule and the block below it.
  *   - Board i of a load or store sits at cells + (i - first) * board_stride + y * row_stride; input
- *     0 / nonzero, output 0 / 255.  No call but create and the first golhip_batch_track_settle(b, 1)
- *     allocates device memory: bytes, seeds, counts and history go through a transfer stage in chunks.
+ *     0 / nonzero, output 0 / 255.  No call but create, the first golhip_batch_track_settle(b, 1) and
+ *     the first golhip_batch_set_rules allocates device memory: bytes, seeds, rules, counts and
+ *     history go through a transfer stage in chunks.
  *   - A batch has ONE turn counter.  Any golhip_batch_load_bytes, even of part of the batch, and any
  *     golhip_batch_init_random set it to 0 and clear every settle record: a batch is filled, then run.
  *   - golhip_batch_init_random: board i is bit for bit what golhip_init_random(seed_i, density_q32)
@@ -442,6 +443,36 @@ int golhip_batch_alive_counts(golhip_batch_t b, uint32_t *out /* nboards */);
 int golhip_batch_track_settle(golhip_batch_t b, int enable);
 int golhip_batch_settled(golhip_batch_t b, int64_t *out /* nboards */);
 int golhip_batch_turn(golhip_batch_t b, int64_t *out);
+/* Life-like rules on a batch: one rule for all boards (golhip_batch_set_rule = golhip_parse_rule +
+ * golhip_batch_set_rule_masks), or one per board (golhip_batch_set_rules: nboards birth masks and
+ * nboards survive masks; both NULL: back to the uniform rule, which per-board rules do not change).
+ * Masks as in golhip_set_rule.  A batch starts at B3/S23.
+ *   - A uniform B3/S23, defaulted or set explicitly, launches gol_batch exactly as it always did.
+ *     Any other rule launches gol_batch_rule -- the same geometry, history, settling and in-place
+ *     update under the rule: a uniform catalogue rule (HighLife B36/S23, Day & Night B3678/S34678,
+ *     Seeds B2/S, Replicator B1357/S1357) constant-folded, every other uniform rule in the table
+ *     form, which is slower.  Per-board rules ALWAYS run the table form, also when they happen to
+ *     be B3/S23 or catalogue rules.  golhip_batch_kernel: what the next step launches, *form = 0
+ *     gol_batch, 1 constant-folded, 2 table, 3 table with per-board rules.
+ *   - Setting a rule keeps the boards, the turn, the history behaviour and the settle switch;
+ *     golhip_batch_load_bytes and golhip_batch_init_random do not touch the rule.
+ *   - A mask with bits above 8 is GOLHIP_ERR_ARG; in a per-board array golhip_batch_last_error(b)
+ *     names the board index and the mask.  A bad rule text is GOLHIP_ERR_ARG naming the text.  The
+ *     handle is untouched either way.
+ *   - The settle record is the record of one rule: with settle tracking on and turn > 0 any change
+ *     of rule is GOLHIP_ERR_STATE (setting the rule the batch already has is no change).  Change
+ *     it at turn 0, i.e. after a load.
+ *   - golhip_batch_get_rule with per-board rules set is GOLHIP_ERR_STATE; golhip_batch_get_rules
+ *     always answers (the uniform rule repeated when no per-board rules are set).
+ *   - B0 rules are allowed, as on the engine: the torus has no dead padding.
+ *   - The per-board rules live in device memory allocated by the first golhip_batch_set_rules and
+ *     are uploaded through the transfer stage. */
+int golhip_batch_set_rule(golhip_batch_t b, const char *rule);
+int golhip_batch_set_rule_masks(golhip_batch_t b, uint32_t birth, uint32_t survive);
+int golhip_batch_get_rule(golhip_batch_t b, uint32_t *birth, uint32_t *survive);
+int golhip_batch_set_rules(golhip_batch_t b, const uint32_t *birth /* nboards */, const uint32_t *survive);
+int golhip_batch_get_rules(golhip_batch_t b, uint32_t *birth /* nboards */, uint32_t *survive);
+int golhip_batch_kernel(golhip_batch_t b, int *form);
 
 #ifdef __cplusplus
 }

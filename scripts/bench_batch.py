@@ -19,6 +19,14 @@ counts=True beside the history modes), timed over --yardstick-boards boards; a b
 set beside B times its median.  --ceiling-json: the JSON line of a bench.py run of the same
 session (its "value", GCUPS at 65536^2), quoted beside the rates.
 
+--rule RULE ("B36/S23", ...): the batch runs that life-like rule (gol_batch_rule: constant-folded for
+a catalogue rule, else the table form; with --per-board-rules the same rule given to every board as
+its own, which always runs the table form).  The yardstick is then the only route there was for
+such a rule: one Engine with set_rule(RULE), per board load() + step(1000) + store().  Every row
+also times the B3/S23 batch (gol_batch) of the same size and mode in the same process and reports
+the rule's call time over it ("vs_life").  --shapes / --batches narrow the run.  Without --rule the
+run and its output are what they always were.
+
 One JSON line on stdout; --out also writes it to a file.  There is no CPU fallback: without a GPU
 the script fails.
 """
@@ -57,23 +65,38 @@ def main():
     ap.add_argument("--yardstick-boards", type=int, default=32)
     ap.add_argument("--ceiling-json", type=Path)
     ap.add_argument("--out", type=Path)
+    ap.add_argument("--rule")
+    ap.add_argument("--per-board-rules", action="store_true")
+    ap.add_argument("--shapes", help="e.g. 64x64,512x512 (default: all three)")
+    ap.add_argument("--batches", help="e.g. 256,4096 (default: 1,256,4096,65536)")
     a = ap.parse_args()
     assert a.calls >= 7
+    assert a.rule or not a.per_board_rules, "--per-board-rules needs --rule"
+    shapes = [tuple(int(v) for v in t.split("x")) for t in a.shapes.split(",")] if a.shapes else SHAPES
+    batches = [int(v) for v in a.batches.split(",")] if a.batches else BATCHES
+    rule = golhip.parse_rule(a.rule) if a.rule else None
     res = {"bench": "batch", "version": golhip.load_library().golhip_version(), "turns": TURNS,
            "calls": a.calls, "shapes": []}
     if a.ceiling_json:
         line = [ln for ln in a.ceiling_json.read_text().splitlines() if ln.startswith("{")][-1]
         res["ceiling_65536sq_gcups"] = json.loads(line)["value"]
+    if rule:
+        res["rule"] = golhip.rule_string(*rule)
+        res["per_board_rules"] = a.per_board_rules
     budget = 16 << 30  # bytes of boards plus their settle copy a batch may take here
-    for w, h in SHAPES:
+    for w, h in shapes:
         cells = w * h
         entry = {"width": w, "height": h, "batches": []}
         # the yardstick: one engine, board after board
         rng = np.random.default_rng(1)
         board = (rng.random((h, w)) < 0.5).astype(np.uint8) * 255
         with golhip.Engine(w, h, k=16) as e:
-            e.set_board_kernel(1)
-            assert e.launch_kind(16)[0] == "board"
+            if rule:
+                e.set_rule(rule)
+                assert e.launch_kind(16)[0] == "rule"
+            else:
+                e.set_board_kernel(1)
+                assert e.launch_kind(16)[0] == "board"
 
             def one(counts):
                 e.load(board)
@@ -88,7 +111,7 @@ def main():
                 y[name] = {"per_board_ms_median": round(med * 1e3, 4), "per_board_ms_min": round(best * 1e3, 4),
                            "gcups": round(cells * TURNS / med / 1e9, 3)}
         entry["engine_loop"] = y
-        for B in BATCHES:
+        for B in batches:
             words = h * max(w, 128) // 32 * 4  # bytes of one packed board
             if B * words * 2 > budget:
                 entry["batches"].append({"boards": B, "skipped": "over 16 GiB of boards"})
@@ -100,6 +123,11 @@ def main():
                     if mode == "history+settle":
                         b.track_settle()
                     hist = mode != "plain"
+                    if rule and a.per_board_rules:
+                        b.set_rules(np.tile(np.array(rule, dtype=np.uint32), (B, 1)))
+                    elif rule:
+                        b.set_rule(rule)
+                    form = b.kernel_form
                     med, best = median_s(lambda: b.step(TURNS, history=hist), 2, a.calls)
                 loop = y["plain" if mode == "plain" else "counts"]["per_board_ms_median"] * 1e-3 * B
                 row[mode] = {"call_ms_median": round(med * 1e3, 3), "call_ms_min": round(best * 1e3, 3),
@@ -107,6 +135,14 @@ def main():
                              "gcups": round(B * cells * TURNS / med / 1e9, 2),
                              "engine_loop_ms": round(loop * 1e3, 3),
                              "speedup_over_engine_loop": round(loop / med, 2)}
+                if rule:  # the B3/S23 batch of the same size and mode, same process
+                    with golhip.Batch(w, h, B) as b:
+                        b.init_random(seed0=1)
+                        if mode == "history+settle":
+                            b.track_settle()
+                        life, _ = median_s(lambda: b.step(TURNS, history=hist), 2, a.calls)
+                    row[mode].update(kernel_form=form, life_call_ms_median=round(life * 1e3, 3),
+                                     vs_life=round(med / life, 3))
             row["settle_cost_ratio"] = round(row["history+settle"]["call_ms_median"] / row["history"]["call_ms_median"], 3)
             entry["batches"].append(row)
             print(json.dumps({"shape": [w, h], **row}), file=sys.stderr, flush=True)
