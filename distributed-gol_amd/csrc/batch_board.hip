@@ -6,9 +6,12 @@
 // blockIdx.x selects the board: board i lives at boards + i * board_pitch words, in the packed
 // layout of a single engine of that size (rows of wd in {4, 8, 16} words, pitch wd).  The geometry
 // is gol_board's (board_common.hpp): W waves, four 16-lane DPP segments per wave, R rows per
-// segment in VGPRs, row_ror:1 for the torus wrap, drifting sums, the segments' edge-row sums
-// through LDS under one LDS-only barrier per generation, K (runtime, <= kBoardMaxK) generations
-// per launch, unrotate16 on the way out.  No trapezoid, no halo, no inter-workgroup traffic.
+// segment in VGPRs, row_ror:1 for the torus wrap, and gol_board's generation step: sums16, then
+// board_gen (the segments' edge-row sums through LDS under one LDS-only barrier per generation);
+// K (runtime, <= kBoardMaxK) generations per launch, unrotate16 on the way out.  No trapezoid, no
+// halo, no inter-workgroup traffic.  gol_batch_rule (batch_rule.hpp) keeps a copy of this kernel's
+// body around the same board_gen: with the two bodies folded into one inlined function the HIST
+// kernels here got another prologue and their calls took up to 6 % longer.
 //
 // A workgroup reads its whole board into registers before it stores anything and every wave
 // stores exactly the rows it loaded, so a launch advances the boards IN PLACE: no second buffer.
@@ -73,45 +76,12 @@ __global__ __launch_bounds__(64 * W) void gol_batch(BatchParams p, int K) {
         }
     }
     const int up = (sg + NSEG - 1) % NSEG, dn = (sg + 1) % NSEG;
-    auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
     // generation g (exchange buffer par): the rows advance in place; returns this lane's alive
     // cells of the new generation (HIST)
     auto gen = [&](int g, int par) -> uint32_t {
         uint32_t s[R], cy[R], ctr[R], nx[R];
         sums16<R>(c, s, cy, ctr);
-        ex[par][sg][0][c16] = s[0];
-        ex[par][sg][1][c16] = cy[0];
-        ex[par][sg][2][c16] = s[R - 1];
-        ex[par][sg][3][c16] = cy[R - 1];
-        if constexpr (R >= 3) {  // the interior rows from the segment's own sums
-            constexpr int NI = R - 2;
-            uint32_t as[NI], acy[NI], ms[NI], mcy[NI], mc[NI], bs[NI], bcy[NI], ni[NI];
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-                as[i] = s[i], acy[i] = cy[i];
-                ms[i] = s[i + 1], mcy[i] = cy[i + 1], mc[i] = ctr[i + 1];
-                bs[i] = s[i + 2], bcy[i] = cy[i + 2];
-            }
-            life_om<NI>(as, acy, ms, mcy, mc, bs, bcy, ni, AllRows{});
-#pragma unroll
-            for (int i = 0; i < NI; ++i) nx[i + 1] = ni[i];
-        }
-        lds_barrier();
-        const uint32_t ts = ex[par][up][2][c16], tcy = ex[par][up][3][c16];  // the row above row 0
-        const uint32_t bts = ex[par][dn][0][c16], btcy = ex[par][dn][1][c16];  // below row R - 1
-        if constexpr (R == 1) {
-            uint32_t as[1] = {ts}, acy[1] = {tcy}, ms[1] = {s[0]}, mcy[1] = {cy[0]}, mc[1] = {ctr[0]};
-            uint32_t bs[1] = {bts}, bcy[1] = {btcy}, n1[1];
-            life_om<1>(as, acy, ms, mcy, mc, bs, bcy, n1, AllRows{});
-            nx[0] = n1[0];
-        } else {
-            uint32_t as[2] = {ts, s[R - 2]}, acy[2] = {tcy, cy[R - 2]};
-            uint32_t ms[2] = {s[0], s[R - 1]}, mcy[2] = {cy[0], cy[R - 1]}, mc[2] = {ctr[0], ctr[R - 1]};
-            uint32_t bs[2] = {s[1], bts}, bcy[2] = {cy[1], btcy}, n2[2];
-            life_om<2>(as, acy, ms, mcy, mc, bs, bcy, n2, AllRows{});
-            nx[0] = n2[0];
-            nx[R - 1] = n2[1];
-        }
+        board_gen<R>(s, cy, ctr, ex, par, sg, up, dn, c16, LifeNext{}, nx);
         uint32_t a = 0;
         if constexpr (HIST)
 #pragma unroll
@@ -213,12 +183,6 @@ hipError_t launch_batch_wr(int K, int nboards, const BatchParams &p, hipStream_t
     else
         hipLaunchKernelGGL((gol_batch<W, R, false, false>), grid, block, 0, s, p, K);
     return hipGetLastError();
-}
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
 }
 
 // init_random_rows (golhip_kernels.hip) for every board of a batch: word for word what a single

@@ -1,16 +1,16 @@
 // batch_rule.hpp -- gol_batch_rule<W, R, HIST, SETTLE, Rule>: gol_batch (batch_board.hip) for
 // life-like rules B.../S..., shared by the per-functor translation units batch_rule_*.hip.
-// gol_batch itself is untouched and B3/S23 never runs this.
+// B3/S23 never runs this.
 //
-// Geometry, contract and LDS protocol are gol_batch's, line for line: the GOLHIP_BOARD_SHAPES
-// table, one workgroup per board advanced in place, the edge-row sums through ex[2][NSEG][4][16]
-// under one LDS-only barrier per generation, HIST partials through cnt[2][4][16] flushed by wave 0
-// one group later, SETTLE through prev / last_diff, groups of 4 generations plus the 0..3
-// remainder, unrotate16 on the way out.  None of that depends on the rule; the settle argument
-// needs a deterministic rule only (once board(t) == board(t - 2) it holds for every later t), so
-// it holds for any fixed rule, B0 rules and their period-2 strobing included.
+// The generation step is sums16 and board_common.hpp's board_gen, as in gol_board and gol_batch.  The
+// body around it -- loads, prev, HIST partials through cnt[2][4][16] flushed by wave 0 one group
+// later, SETTLE through prev / last_diff, groups of 4 generations plus the 0..3 remainder,
+// unrotate16 on the way out -- is gol_batch's, kept as a second copy (batch_board.hip says why) and
+// described there.  None of it depends on the rule; the settle argument needs a deterministic rule
+// only (once board(t) == board(t - 2) it holds for every later t), so it holds for any fixed rule,
+// B0 rules and their period-2 strobing included.
 //
-// The one difference: where gol_batch calls life_om, rule_om forms the sum bits o, k, p, q of a
+// The one difference: where gol_batch's rule step is life_om, rule_om forms the sum bits o, k, p, q of a
 // few rows op-major (four v_bitop3 per row, as life_om does) and hands each row to the functor of
 // golhip_rule.hpp -- RuleConst<B, S> (7 v_bitop3, truth tables as immediates) for a catalogue rule,
 // RuleTable (22 v_bitop3, the 18 rule bits expanded to 0 / ~0 words once per wave) for every other
@@ -65,10 +65,22 @@ __device__ __forceinline__ void rule_om(const Rule &rule, const uint32_t (&as)[N
     }
 }
 
+// `rule` as board_gen's rule step.
+template <class Rule>
+struct RuleNext {
+    Rule rule;
+    template <int N>
+    __device__ __forceinline__ void operator()(const uint32_t (&as)[N], const uint32_t (&acy)[N],
+                                               const uint32_t (&ms)[N], const uint32_t (&mcy)[N],
+                                               const uint32_t (&mc)[N], const uint32_t (&bs)[N],
+                                               const uint32_t (&bcy)[N], uint32_t (&out)[N]) const {
+        rule_om<N, kRuleInterleave<Rule>>(rule, as, acy, ms, mcy, mc, bs, bcy, out);
+    }
+};
+
 template <int W, int R, bool HIST, bool SETTLE, class Rule>
 __global__ __launch_bounds__(64 * W) void gol_batch_rule(BatchRuleParams rp, int K) {
     constexpr int NSEG = 4 * W;
-    constexpr int IW = kRuleInterleave<Rule>;
     const BatchParams &p = rp.b;
     __shared__ uint32_t ex[2][NSEG][4][16];
     __shared__ uint32_t cnt[2][4][16];
@@ -89,7 +101,7 @@ __global__ __launch_bounds__(64 * W) void gol_batch_rule(BatchRuleParams rp, int
         rm.birth = rp.rules[2 * (int64_t)blockIdx.x];
         rm.survive = rp.rules[2 * (int64_t)blockIdx.x + 1];
     }
-    const Rule rule(rm);
+    const RuleNext<Rule> next{Rule(rm)};
     uint32_t c[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) c[r] = board[(sg * R + r) * wd + (c16 & (wd - 1))];
@@ -104,45 +116,12 @@ __global__ __launch_bounds__(64 * W) void gol_batch_rule(BatchRuleParams rp, int
         }
     }
     const int up = (sg + NSEG - 1) % NSEG, dn = (sg + 1) % NSEG;
-    auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
     // generation g (exchange buffer par): the rows advance in place; returns this lane's alive
     // cells of the new generation (HIST)
     auto gen = [&](int g, int par) -> uint32_t {
         uint32_t s[R], cy[R], ctr[R], nx[R];
         sums16<R>(c, s, cy, ctr);
-        ex[par][sg][0][c16] = s[0];
-        ex[par][sg][1][c16] = cy[0];
-        ex[par][sg][2][c16] = s[R - 1];
-        ex[par][sg][3][c16] = cy[R - 1];
-        if constexpr (R >= 3) {  // the interior rows from the segment's own sums
-            constexpr int NI = R - 2;
-            uint32_t as[NI], acy[NI], ms[NI], mcy[NI], mc[NI], bs[NI], bcy[NI], ni[NI];
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-                as[i] = s[i], acy[i] = cy[i];
-                ms[i] = s[i + 1], mcy[i] = cy[i + 1], mc[i] = ctr[i + 1];
-                bs[i] = s[i + 2], bcy[i] = cy[i + 2];
-            }
-            rule_om<NI, IW>(rule, as, acy, ms, mcy, mc, bs, bcy, ni);
-#pragma unroll
-            for (int i = 0; i < NI; ++i) nx[i + 1] = ni[i];
-        }
-        lds_barrier();
-        const uint32_t ts = ex[par][up][2][c16], tcy = ex[par][up][3][c16];  // the row above row 0
-        const uint32_t bts = ex[par][dn][0][c16], btcy = ex[par][dn][1][c16];  // below row R - 1
-        if constexpr (R == 1) {
-            uint32_t as[1] = {ts}, acy[1] = {tcy}, ms[1] = {s[0]}, mcy[1] = {cy[0]}, mc[1] = {ctr[0]};
-            uint32_t bs[1] = {bts}, bcy[1] = {btcy}, n1[1];
-            rule_om<1, IW>(rule, as, acy, ms, mcy, mc, bs, bcy, n1);
-            nx[0] = n1[0];
-        } else {
-            uint32_t as[2] = {ts, s[R - 2]}, acy[2] = {tcy, cy[R - 2]};
-            uint32_t ms[2] = {s[0], s[R - 1]}, mcy[2] = {cy[0], cy[R - 1]}, mc[2] = {ctr[0], ctr[R - 1]};
-            uint32_t bs[2] = {s[1], bts}, bcy[2] = {cy[1], btcy}, n2[2];
-            rule_om<2, IW>(rule, as, acy, ms, mcy, mc, bs, bcy, n2);
-            nx[0] = n2[0];
-            nx[R - 1] = n2[1];
-        }
+        board_gen<R>(s, cy, ctr, ex, par, sg, up, dn, c16, next, nx);
         uint32_t a = 0;
         if constexpr (HIST)
 #pragma unroll

@@ -1,6 +1,7 @@
-// board_common.hpp -- the device helpers of the whole-torus-in-one-workgroup geometry, shared by
-// gol_board (stencil_board.hip: one board per launch) and gol_batch (batch_board.hip: one board per
-// workgroup of the grid), and the (W waves, R rows per segment) table both use.
+// board_common.hpp -- the whole-torus-in-one-workgroup geometry: its device helpers, the (W waves,
+// R rows per segment) table, the one generation step (board_gen) behind gol_board
+// (stencil_board.hip: one board per launch), gol_batch (batch_board.hip) and gol_batch_rule
+// (batch_rule.hpp): one board per workgroup of the grid.
 //
 // Layout: a wave's 64 lanes are four 16-lane DPP rows ("segments"); segment sg = 4 w + (lane / 16)
 // holds board rows [sg R, sg R + R), one row per VGPR, lane l % 16 holding word (l % 16) % wd of
@@ -63,6 +64,73 @@ __device__ __forceinline__ void wave_sum_dpp_n(uint32_t (&v)[N]) {
 // (W, R) by board height, first match: 4 W R == height.  16 waves while the rows allow (4 per SIMD
 // hide the VALU latency of each wave's R independent rows), then fewer.
 #define GOLHIP_BOARD_SHAPES(X) X(16, 8) X(16, 4) X(8, 4) X(4, 4) X(2, 4) X(1, 4) X(1, 2) X(1, 1)
+
+// The workgroup barrier of a generation: it orders LDS traffic only, so it waits for lgkmcnt and
+// leaves the global loads and stores in flight.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// B3/S23 as board_gen's rule step.
+struct LifeNext {
+    template <int N>
+    __device__ __forceinline__ void operator()(const uint32_t (&as)[N], const uint32_t (&acy)[N],
+                                               const uint32_t (&ms)[N], const uint32_t (&mcy)[N],
+                                               const uint32_t (&mc)[N], const uint32_t (&bs)[N],
+                                               const uint32_t (&bcy)[N], uint32_t (&out)[N]) const {
+        life_om<N>(as, acy, ms, mcy, mc, bs, bcy, out, AllRows{});
+    }
+};
+
+// One generation of segment sg's R rows from their sums16 (s, cy, ctr): nx = the next generation,
+// one bit further east.  The caller runs sums16 itself and keeps ctr (the old rows in nx's frame,
+// which SETTLE and gol_board's LD need): with sums16 in here and ctr handed back, the compiler
+// ordered the loops of the SETTLE-only batch kernels differently and they ran 2-4 % slower; this
+// way gol_batch and the catalogue kernels compile to the code they had with the step written out
+// in each kernel.  A segment's edge rows need
+// the sums of the segments above (up) and below (dn): every segment puts the sums of its own edge
+// rows into ex[par], computes its interior rows while they travel, and reads its neighbours' after
+// ONE LDS-only barrier.  ex is double-buffered by generation parity: a wave that is a generation
+// ahead writes ex[par ^ 1], and cannot reach its next write of ex[par] before every wave has passed
+// the barrier between -- after its reads of ex[par], which the barrier's lgkmcnt(0) completes.
+// The rule enters only as next.template operator()<N>(as, acy, ms, mcy, mc, bs, bcy, out): the
+// sums of the rows above, of the rows themselves with their centres, and of the rows below -> out.
+template <int R, int NSEG, class Next>
+__device__ __forceinline__ void board_gen(const uint32_t (&s)[R], const uint32_t (&cy)[R], const uint32_t (&ctr)[R],
+                                          uint32_t (&ex)[2][NSEG][4][16], int par, int sg, int up, int dn, int c16,
+                                          const Next &next, uint32_t (&nx)[R]) {
+    ex[par][sg][0][c16] = s[0];
+    ex[par][sg][1][c16] = cy[0];
+    ex[par][sg][2][c16] = s[R - 1];
+    ex[par][sg][3][c16] = cy[R - 1];
+    if constexpr (R >= 3) {  // the interior rows from the segment's own sums
+        constexpr int NI = R - 2;
+        uint32_t as[NI], acy[NI], ms[NI], mcy[NI], mc[NI], bs[NI], bcy[NI], ni[NI];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            as[i] = s[i], acy[i] = cy[i];
+            ms[i] = s[i + 1], mcy[i] = cy[i + 1], mc[i] = ctr[i + 1];
+            bs[i] = s[i + 2], bcy[i] = cy[i + 2];
+        }
+        next.template operator()<NI>(as, acy, ms, mcy, mc, bs, bcy, ni);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) nx[i + 1] = ni[i];
+    }
+    lds_barrier();
+    const uint32_t ts = ex[par][up][2][c16], tcy = ex[par][up][3][c16];  // the row above row 0
+    const uint32_t bts = ex[par][dn][0][c16], btcy = ex[par][dn][1][c16];  // below row R - 1
+    if constexpr (R == 1) {
+        uint32_t as[1] = {ts}, acy[1] = {tcy}, ms[1] = {s[0]}, mcy[1] = {cy[0]}, mc[1] = {ctr[0]};
+        uint32_t bs[1] = {bts}, bcy[1] = {btcy}, n1[1];
+        next.template operator()<1>(as, acy, ms, mcy, mc, bs, bcy, n1);
+        nx[0] = n1[0];
+    } else {
+        uint32_t as[2] = {ts, s[R - 2]}, acy[2] = {tcy, cy[R - 2]};
+        uint32_t ms[2] = {s[0], s[R - 1]}, mcy[2] = {cy[0], cy[R - 1]}, mc[2] = {ctr[0], ctr[R - 1]};
+        uint32_t bs[2] = {s[1], bts}, bcy[2] = {cy[1], btcy}, n2[2];
+        next.template operator()<2>(as, acy, ms, mcy, mc, bs, bcy, n2);
+        nx[0] = n2[0];
+        nx[R - 1] = n2[1];
+    }
+}
 
 }  // namespace
 }  // namespace golhip

@@ -36,6 +36,14 @@ __host__ __device__ inline int64_t act_same_off(int64_t G) { return 8 * G; }
 __host__ __device__ inline int64_t act_pop_off(int64_t G) { return 9 * G; }
 constexpr int kActStatSlots = 64;  // StencilParams::act_stats: [computed x 64][skipped x 64]
 
+// The mixer of init_random_rows (golhip_kernels.hip) and batch_init_random (batch_board.hip): one
+// definition, so that a batch's board i is word for word the single engine's board of seed_i.
+__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
 struct StencilParams {
     int64_t pitch;       // words between consecutive rows
     int64_t r0b, r0e;    // output range 0

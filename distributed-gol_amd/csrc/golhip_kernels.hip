@@ -84,12 +84,6 @@ __global__ void unpack_rows(const uint32_t *__restrict__ row0, int64_t pitch, in
     }
 }
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
 __global__ void init_random_rows(uint32_t *__restrict__ row0, int64_t pitch, int64_t rows,
                                  int64_t gy0, int64_t width, int32_t wd, uint64_t seed,
                                  uint32_t density) {

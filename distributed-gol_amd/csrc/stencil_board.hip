@@ -21,8 +21,9 @@
 // neighbours are the next VGPR of the same lane; a segment's edge rows' SUMS go through LDS to the
 // segments above and below (double-buffered by generation parity, one LDS-only barrier per
 // generation), as in gol_slab2: the interior rows are computed before the barrier.
-// The lane layout's device helpers (west16, sums16, unrotate16, wave_sum_dpp_n) and the (W, R) table
-// are in board_common.hpp, shared with gol_batch (batch_board.hip).
+// That generation step (board_gen), the lane layout's device helpers (west16, sums16, unrotate16,
+// wave_sum_dpp_n) and the (W, R) table are in board_common.hpp, shared with gol_batch
+// (batch_board.hip) and gol_batch_rule (batch_rule.hpp); this file adds the COUNT slots and LD flips.
 #include "board_common.hpp"
 
 namespace golhip {
@@ -50,46 +51,13 @@ __global__ __launch_bounds__(64 * W) void gol_board(const uint32_t *__restrict__
 #pragma unroll
     for (int r = 0; r < R; ++r) c[r] = in[(int64_t)(sg * R + r) * p.pitch + c16 % wd];
     const int up = (sg + NSEG - 1) % NSEG, dn = (sg + 1) % NSEG;
-    auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
     uint32_t dlast[LD ? R : 1];  // LD: the last generation's flips (drifted frame)
     // generation g (exchange buffer par = g & 1): the rows advance in place; returns this lane's
     // alive cells of the new generation (COUNT)
     auto gen = [&](int g, int par) -> uint32_t {
         uint32_t s[R], cy[R], ctr[R], nx[R];
         sums16<R>(c, s, cy, ctr);
-        ex[par][sg][0][c16] = s[0];
-        ex[par][sg][1][c16] = cy[0];
-        ex[par][sg][2][c16] = s[R - 1];
-        ex[par][sg][3][c16] = cy[R - 1];
-        if constexpr (R >= 3) {  // the interior rows from the segment's own sums
-            constexpr int NI = R - 2;
-            uint32_t as[NI], acy[NI], ms[NI], mcy[NI], mc[NI], bs[NI], bcy[NI], ni[NI];
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-                as[i] = s[i], acy[i] = cy[i];
-                ms[i] = s[i + 1], mcy[i] = cy[i + 1], mc[i] = ctr[i + 1];
-                bs[i] = s[i + 2], bcy[i] = cy[i + 2];
-            }
-            life_om<NI>(as, acy, ms, mcy, mc, bs, bcy, ni, AllRows{});
-#pragma unroll
-            for (int i = 0; i < NI; ++i) nx[i + 1] = ni[i];
-        }
-        lds_barrier();
-        const uint32_t ts = ex[par][up][2][c16], tcy = ex[par][up][3][c16];  // the row above row 0
-        const uint32_t bts = ex[par][dn][0][c16], btcy = ex[par][dn][1][c16];  // below row R - 1
-        if constexpr (R == 1) {
-            uint32_t as[1] = {ts}, acy[1] = {tcy}, ms[1] = {s[0]}, mcy[1] = {cy[0]}, mc[1] = {ctr[0]};
-            uint32_t bs[1] = {bts}, bcy[1] = {btcy}, n1[1];
-            life_om<1>(as, acy, ms, mcy, mc, bs, bcy, n1, AllRows{});
-            nx[0] = n1[0];
-        } else {
-            uint32_t as[2] = {ts, s[R - 2]}, acy[2] = {tcy, cy[R - 2]};
-            uint32_t ms[2] = {s[0], s[R - 1]}, mcy[2] = {cy[0], cy[R - 1]}, mc[2] = {ctr[0], ctr[R - 1]};
-            uint32_t bs[2] = {s[1], bts}, bcy[2] = {cy[1], btcy}, n2[2];
-            life_om<2>(as, acy, ms, mcy, mc, bs, bcy, n2, AllRows{});
-            nx[0] = n2[0];
-            nx[R - 1] = n2[1];
-        }
+        board_gen<R>(s, cy, ctr, ex, par, sg, up, dn, c16, LifeNext{}, nx);
         uint32_t a = 0;
         if constexpr (COUNT)
 #pragma unroll
