@@ -15,8 +15,15 @@
 // whatever they are.  golhip_batch_kernel reports which.  The settle record is the record of one
 // rule, so with tracking on the rule changes at turn 0 only.
 //
+// Period tracking (golhip_batch_track_period) swaps every one of those launches for gol_batch_period
+// (batch_period.hpp) under the same rule: per-board Brent cycle detection, a snapshot buffer beside
+// the boards and one int64 per board.  golhip_batch_kernel's form still names the rule form.  It
+// excludes settle tracking (one tracker per launch keeps the kernel count down), and its record
+// too is the record of one rule.
+//
 // Device memory is allocated at create (the boards, the per-board counters, the transfer stage), by
-// the first golhip_batch_track_settle(b, 1) (board(t - 1) of every board) and by the first
+// the first golhip_batch_track_settle(b, 1) (board(t - 1) of every board), by the first
+// golhip_batch_track_period(b, 1) (every board's snapshot and its repeat turn) and by the first
 // golhip_batch_set_rules (the per-board rule pairs); no other call allocates.  Bytes in and out,
 // the seeds of init_random, per-board rules and counts and the per-turn history all pass through
 // the stage in chunks.
@@ -43,6 +50,9 @@ struct golhip_batch {
     uint8_t *stage = nullptr;
     int64_t stage_bytes = 0;
     bool track = false;
+    uint32_t *snap = nullptr;        // period tracking: board(2^j - 1) of every board, the Brent snapshot
+    int64_t *repeat_turn = nullptr;  // first turn t with board(t) == board(s(t)); -1: none yet
+    bool track_period = false;
     int64_t turn = 0;
     golhip::RuleMasks rule{golhip::kLifeBirth, golhip::kLifeSurvive};  // the uniform rule
     bool per_board = false;              // the boards run `rules`, not `rule`
@@ -81,11 +91,14 @@ void batch_free(golhip_batch_t b) {
     if (b->boards) (void)hipFree(b->boards);
     if (b->prev) (void)hipFree(b->prev);
     if (b->last_diff) (void)hipFree(b->last_diff);
+    if (b->snap) (void)hipFree(b->snap);
+    if (b->repeat_turn) (void)hipFree(b->repeat_turn);
     if (b->stage) (void)hipFree(b->stage);
     if (b->rules) (void)hipFree(b->rules);
     if (b->stream) (void)hipStreamDestroy(b->stream);
-    b->boards = b->prev = b->rules = nullptr;
+    b->boards = b->prev = b->rules = b->snap = nullptr;
     b->last_diff = nullptr;
+    b->repeat_turn = nullptr;
     b->stage = nullptr;
     b->stream = nullptr;
 }
@@ -113,11 +126,13 @@ int batch_alloc(golhip_batch_t b) {
     return GOLHIP_OK;
 }
 
-// A new set of boards: turn 0, no settle record.
+// A new set of boards: turn 0, no settle record, no repeat.
 int boards_replaced(golhip_batch_t b) {
     b->turn = 0;
     if (b->last_diff)
         BHIPCHK(b, hipMemsetAsync(b->last_diff, 0, sizeof(unsigned long long) * (size_t)b->nboards, b->stream));
+    if (b->repeat_turn)  // every byte 0xff: -1
+        BHIPCHK(b, hipMemsetAsync(b->repeat_turn, 0xff, sizeof(int64_t) * (size_t)b->nboards, b->stream));
     return GOLHIP_OK;
 }
 
@@ -168,11 +183,15 @@ int kernel_form(const golhip_batch *b) {
     return rule_catalogued(b->rule.birth, b->rule.survive) ? 1 : 2;
 }
 
-// The settle record (last_diff, prev) describes the boards under one rule.
+// The settle record (last_diff, prev) and the period record (repeat_turn, snap) describe the boards
+// under one rule.
 int rule_change_allowed(golhip_batch_t b) {
     if (b->track && b->turn > 0)
         return bfail(b, GOLHIP_ERR_STATE, "settle tracking is on at turn %lld: the settle record holds under one rule, "
                      "change the rule at turn 0 (after a load)", (long long)b->turn);
+    if (b->track_period && b->turn > 0)
+        return bfail(b, GOLHIP_ERR_STATE, "period tracking is on at turn %lld: a repeat means a cycle under one rule "
+                     "only, change the rule at turn 0 (after a load)", (long long)b->turn);
     return GOLHIP_OK;
 }
 
@@ -289,7 +308,10 @@ int golhip_batch_step(golhip_batch_t b, int64_t turns, uint32_t *history, size_t
     for (int64_t done = 0; done < turns;) {
         const int K = (int)std::min<int64_t>(kmax, turns - done);
         p.t0 = b->turn;
-        if (form == 0) {
+        if (b->track_period) {  // every rule form, B3/S23 included: the period kernels
+            const BatchPeriodParams pp{p, b->rule, b->per_board ? b->rules : nullptr, b->snap, b->repeat_turn};
+            BHIPCHK(b, launch_batch_period(K, b->W, b->R, b->nboards, pp, b->stream));
+        } else if (form == 0) {
             BHIPCHK(b, launch_batch_board(K, b->W, b->R, b->nboards, p, b->stream));
         } else {  // a missing kernel is an error, never gol_batch
             const BatchRuleParams rp{p, b->rule, b->per_board ? b->rules : nullptr};
@@ -325,6 +347,9 @@ int golhip_batch_track_settle(golhip_batch_t b, int enable) {
         return GOLHIP_OK;
     }
     if (b->track) return GOLHIP_OK;
+    if (b->track_period)
+        return bfail(b, GOLHIP_ERR_STATE, "period tracking is on: settle tracking and period tracking exclude each "
+                     "other (golhip_batch_track_period(b, 0) first)");
     if (b->turn != 0)
         return bfail(b, GOLHIP_ERR_STATE, "settle tracking starts at turn 0 (turn %lld): enable it after a load, "
                      "before the first step", (long long)b->turn);
@@ -351,6 +376,53 @@ int golhip_batch_settled(golhip_batch_t b, int64_t *out) {
     for (int i = 0; i < b->nboards; ++i) {
         const int64_t t = std::max<int64_t>(out[i], 1) + 1;
         out[i] = t <= b->turn ? t : -1;
+    }
+    return GOLHIP_OK;
+}
+
+int golhip_batch_track_period(golhip_batch_t b, int enable) {
+    if (!b) return GOLHIP_ERR_ARG;
+    if (!enable) {
+        b->track_period = false;
+        return GOLHIP_OK;
+    }
+    if (b->track_period) return GOLHIP_OK;
+    if (b->track)
+        return bfail(b, GOLHIP_ERR_STATE, "settle tracking is on: period tracking and settle tracking exclude each "
+                     "other (golhip_batch_track_settle(b, 0) first)");
+    if (b->turn != 0)
+        return bfail(b, GOLHIP_ERR_STATE, "period tracking starts at turn 0 (turn %lld): board(0) is the first "
+                     "snapshot, enable it after a load, before the first step", (long long)b->turn);
+    BHIPCHK(b, hipSetDevice(b->device));
+    if (!b->snap) BHIPCHK(b, hipMalloc(&b->snap, sizeof(uint32_t) * (size_t)b->board_words * (size_t)b->nboards));
+    if (!b->repeat_turn) BHIPCHK(b, hipMalloc(&b->repeat_turn, sizeof(int64_t) * (size_t)b->nboards));
+    BHIPCHK(b, hipMemsetAsync(b->repeat_turn, 0xff, sizeof(int64_t) * (size_t)b->nboards, b->stream));
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    b->track_period = true;
+    return GOLHIP_OK;
+}
+
+int golhip_batch_periods(golhip_batch_t b, int64_t *repeat_turn, int64_t *period) {
+    if (!b) return GOLHIP_ERR_ARG;
+    if (!b->track_period) return bfail(b, GOLHIP_ERR_STATE, "period tracking is off (golhip_batch_track_period)");
+    if (!repeat_turn && !period) return GOLHIP_OK;
+    BHIPCHK(b, hipSetDevice(b->device));
+    std::vector<int64_t> own;
+    int64_t *rt = repeat_turn;
+    if (!rt) {
+        own.resize((size_t)b->nboards);
+        rt = own.data();
+    }
+    BHIPCHK(b, hipMemcpyAsync(rt, b->repeat_turn, sizeof(int64_t) * (size_t)b->nboards, hipMemcpyDeviceToHost,
+                              b->stream));
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    if (period) {  // t - s(t), s(t) = 2^floor(log2 t) - 1: the snapshot turn of the window t lies in
+        for (int i = 0; i < b->nboards; ++i) {
+            const int64_t t = rt[i];
+            int64_t top = 1;
+            while (t > 0 && 2 * top <= t) top *= 2;
+            period[i] = t > 0 ? t - (top - 1) : -1;
+        }
     }
     return GOLHIP_OK;
 }

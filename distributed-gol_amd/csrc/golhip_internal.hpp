@@ -323,6 +323,26 @@ hipError_t launch_batch_rule(int K, int W, int R, int nboards, const BatchRulePa
                                            hipStream_t s);
 GOLHIP_RULE_CATALOGUE(GOLHIP_X)
 #undef GOLHIP_X
+// The batch kernel with per-board cycle detection (gol_batch_period, batch_period.hpp; one
+// translation unit per functor, batch_period_*.hip): gol_batch's contract (b, without prev /
+// last_diff) under `rule` or, with rules != null, per-board rules as in BatchRuleParams -- B3/S23
+// included, which runs gol_batch's rule step.  snap (the layout of boards) holds every board's
+// Brent snapshot board(2^j - 1), repeat_turn[i] the first turn at which board i equalled its
+// snapshot (-1: none yet); both live across launches, b.t0 carries the turn.
+struct BatchPeriodParams {
+    BatchParams b;
+    RuleMasks rule;
+    const uint32_t *rules;
+    uint32_t *snap;
+    int64_t *repeat_turn;
+};
+hipError_t launch_batch_period(int K, int W, int R, int nboards, const BatchPeriodParams &pp, hipStream_t s);
+hipError_t launch_batch_period_life(int K, int W, int R, int nboards, const BatchPeriodParams &pp, hipStream_t s);
+#define GOLHIP_X(B, S)                                                                                        \
+    hipError_t launch_batch_period_##B##_##S(int K, int W, int R, int nboards, const BatchPeriodParams &pp, \
+                                             hipStream_t s);
+GOLHIP_RULE_CATALOGUE(GOLHIP_X)
+#undef GOLHIP_X
 // init_random_rows for every board: board i from seeds ? seeds[i] (device memory) : seed0 + i.
 hipError_t launch_batch_init_random(uint32_t *boards, int64_t board_pitch, int64_t nboards, int64_t rows,
                                     int64_t width, int32_t wd, const uint64_t *seeds, uint64_t seed0,

@@ -62,6 +62,7 @@ EXPORTS = [
     "golhip_batch_track_settle", "golhip_batch_settled", "golhip_batch_turn",
     "golhip_batch_set_rule", "golhip_batch_set_rule_masks", "golhip_batch_get_rule", "golhip_batch_set_rules",
     "golhip_batch_get_rules", "golhip_batch_kernel",
+    "golhip_batch_track_period", "golhip_batch_periods",
 ]
 
 
@@ -246,6 +247,8 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
         "golhip_batch_alive_counts": ([H, ctypes.c_void_p], i32),
         "golhip_batch_track_settle": ([H, i32], i32),
         "golhip_batch_settled": ([H, ctypes.c_void_p], i32),
+        "golhip_batch_track_period": ([H, i32], i32),
+        "golhip_batch_periods": ([H, ctypes.c_void_p, ctypes.c_void_p], i32),
         "golhip_batch_turn": ([H, i64p], i32),
         "golhip_batch_set_rule": ([H, ctypes.c_char_p], i32),
         "golhip_batch_set_rule_masks": ([H, ctypes.c_uint32, ctypes.c_uint32], i32),
@@ -803,7 +806,7 @@ class Batch:
     """One golhip_batch handle: `nboards` independent tori of one small size on one device, all
     advanced by one launch (one workgroup per board).  Sizes: widths whose lcm with 128 is 128, 256
     or 512 (16, 64, 128, 256, 512, ...) and 4, 8, 16, ..., 512 rows.  The batch has one turn counter;
-    any load() or init_random() sets it to 0 and clears the settle records.
+    any load() or init_random() sets it to 0 and clears the settle and period records.
 
     The rule is B3/S23 unless `rule` ("B36/S23" or (birth, survive) masks: one life-like rule for all
     boards) or `rules` (one per board) is given, or set later with set_rule() / set_rules().  A
@@ -934,6 +937,21 @@ class Batch:
         self._check(self._L.golhip_batch_settled(self._h, out.ctypes.data))
         return out
 
+    def track_period(self, on: bool = True):
+        """Period tracking (golhip_batch_track_period): per-board cycle detection on the device, for
+        any rule.  Enable it after a load, before the first step; not together with track_settle."""
+        self._check(self._L.golhip_batch_track_period(self._h, int(on)))
+
+    def periods(self) -> tuple[np.ndarray, np.ndarray]:
+        """(repeat_turn, period), int64 per board.  With s(t) = 2 ** floor(log2 t) - 1, repeat_turn is
+        the smallest turn t >= 1 run so far with board(t) == board(s(t)) and period = repeat_turn -
+        s(repeat_turn), exactly the period of the cycle the board has entered; both -1 until then.
+        An empty board or a still life is (1, 1), a lone blinker (3, 2)."""
+        repeat_turn = np.zeros(self.nboards, dtype=np.int64)
+        period = np.zeros(self.nboards, dtype=np.int64)
+        self._check(self._L.golhip_batch_periods(self._h, repeat_turn.ctypes.data, period.ctypes.data))
+        return repeat_turn, period
+
     @property
     def turn(self) -> int:
         v = ctypes.c_int64()
@@ -943,7 +961,8 @@ class Batch:
     # -- the rule
     def set_rule(self, rule: str | tuple[int, int]):
         """One rule for all boards (golhip_batch_set_rule): "B36/S23" or (birth, survive) masks.  Keeps
-        the boards, the turn and the settle switch; with settle tracking on, only at turn 0."""
+        the boards, the turn and the tracking switches; with settle or period tracking on, only at
+        turn 0."""
         if isinstance(rule, (str, bytes)):
             self._check(self._L.golhip_batch_set_rule(self._h, rule.encode() if isinstance(rule, str) else rule))
         else:

@@ -414,11 +414,12 @@ int golhip_edge_wait(golhip_t h, double *total_ms, int64_t *blocks);
  *     what it had.  One device per handle: several GPUs are several handles.
  *   - The rule is B3/S23 unless one is set: golhip_batch_set_rule and the block below it.
  *   - Board i of a load or store sits at cells + (i - first) * board_stride + y * row_stride; input
- *     0 / nonzero, output 0 / 255.  No call but create, the first golhip_batch_track_settle(b, 1) and
- *     the first golhip_batch_set_rules allocates device memory: bytes, seeds, rules, counts and
+ *     0 / nonzero, output 0 / 255.  No call but create, the first golhip_batch_track_settle(b, 1), the
+ *     first golhip_batch_track_period(b, 1) (a second boards-sized buffer, the snapshots, and one
+ *     int64 per board) and the first golhip_batch_set_rules allocates device memory: bytes, seeds, rules, counts and
  *     history go through a transfer stage in chunks.
  *   - A batch has ONE turn counter.  Any golhip_batch_load_bytes, even of part of the batch, and any
- *     golhip_batch_init_random set it to 0 and clear every settle record: a batch is filled, then run.
+ *     golhip_batch_init_random set it to 0 and clear every settle and period record: a batch is filled, then run.
  *   - golhip_batch_init_random: board i is bit for bit what golhip_init_random(seed_i, density_q32)
  *     gives a single engine of that size, seed_i = seeds ? seeds[i] : seed0 + i (width % 64 == 0).
  *   - golhip_batch_step runs `turns` generations of every board and returns when they are done.
@@ -427,7 +428,26 @@ int golhip_edge_wait(golhip_t h, double *total_ms, int64_t *blocks);
  *   - Settling: with tracking on, settled[i] is the smallest absolute turn t >= 2 with
  *     board_i(t) == board_i(t - 2), or -1 while no such turn has been run; once set it never changes,
  *     and it does not depend on how the turns were cut into calls.  Tracking starts at turn 0:
- *     enabling it after turns have run is GOLHIP_ERR_STATE, golhip_batch_settled without it too. */
+ *     enabling it after turns have run is GOLHIP_ERR_STATE, golhip_batch_settled without it too.
+ *   - Periods (golhip_batch_track_period / golhip_batch_periods): per-board cycle detection on the
+ *     device, Brent's scheme with snapshots at turns 2^j - 1, for whatever rule or rules the batch
+ *     runs.  For t >= 1 let s(t) = 2^floor(log2 t) - 1 (0 for t = 1, 1 for t = 2..3, 3 for t = 4..7,
+ *     7 for t = 8..15, ...).  Board i repeats at turn t when board_i(t) == board_i(s(t)) over the
+ *     whole torus; repeat_turn[i] is the smallest such t among the turns run so far and period[i] =
+ *     repeat_turn[i] - s(repeat_turn[i]); both are -1 until a repeat has been run.  The rule is
+ *     deterministic, so period[i] is exactly the period p of the cycle the board has entered, not
+ *     a multiple of it: offsets inside a window only run up to the window's length, so the first
+ *     match has offset p.  With m the first turn inside the cycle, the repeat is found at t =
+ *     2^j - 1 + p for the first j with 2^j - 1 >= m and 2^j >= p: under 2 max(m + 1, p) + p turns.
+ *     An empty or still-life board is (1, 1), a lone blinker (3, 2), a lone glider on a 16 x 16
+ *     torus (p = 64) is (127, 64).  The records depend on the boards and the rule only: not on the
+ *     sizes of the step calls, the launch depths, history on or off or GOLHIP_STAGE_BYTES.
+ *     Enabling is legal at turn 0 only (GOLHIP_ERR_STATE otherwise): board(0) is the first
+ *     snapshot.  golhip_batch_periods with tracking off is GOLHIP_ERR_STATE; either output may be
+ *     NULL.  Period and settle tracking exclude each other: enabling one while the other is on is
+ *     GOLHIP_ERR_STATE (switch the other off first).  They agree where both speak: a board with
+ *     period <= 2 has settled = m + 2.  With period tracking on every rule form, B3/S23 included,
+ *     launches gol_batch_period; golhip_batch_kernel still reports the rule form. */
 typedef struct golhip_batch *golhip_batch_t;
 int golhip_batch_create(int width, int height, int nboards, int device, golhip_batch_t *out);
 int golhip_batch_destroy(golhip_batch_t b);
@@ -442,6 +462,9 @@ int golhip_batch_step(golhip_batch_t b, int64_t turns, uint32_t *history, size_t
 int golhip_batch_alive_counts(golhip_batch_t b, uint32_t *out /* nboards */);
 int golhip_batch_track_settle(golhip_batch_t b, int enable);
 int golhip_batch_settled(golhip_batch_t b, int64_t *out /* nboards */);
+int golhip_batch_track_period(golhip_batch_t b, int enable);
+int golhip_batch_periods(golhip_batch_t b, int64_t *repeat_turn /* nboards, or NULL */,
+                         int64_t *period /* nboards, or NULL */);
 int golhip_batch_turn(golhip_batch_t b, int64_t *out);
 /* Life-like rules on a batch: one rule for all boards (golhip_batch_set_rule = golhip_parse_rule +
  * golhip_batch_set_rule_masks), or one per board (golhip_batch_set_rules: nboards birth masks and
@@ -454,14 +477,14 @@ int golhip_batch_turn(golhip_batch_t b, int64_t *out);
  *     form, which is slower.  Per-board rules ALWAYS run the table form, also when they happen to
  *     be B3/S23 or catalogue rules.  golhip_batch_kernel: what the next step launches, *form = 0
  *     gol_batch, 1 constant-folded, 2 table, 3 table with per-board rules.
- *   - Setting a rule keeps the boards, the turn, the history behaviour and the settle switch;
+ *   - Setting a rule keeps the boards, the turn, the history behaviour and the settle and period switches;
  *     golhip_batch_load_bytes and golhip_batch_init_random do not touch the rule.
  *   - A mask with bits above 8 is GOLHIP_ERR_ARG; in a per-board array golhip_batch_last_error(b)
  *     names the board index and the mask.  A bad rule text is GOLHIP_ERR_ARG naming the text.  The
  *     handle is untouched either way.
- *   - The settle record is the record of one rule: with settle tracking on and turn > 0 any change
- *     of rule is GOLHIP_ERR_STATE (setting the rule the batch already has is no change).  Change
- *     it at turn 0, i.e. after a load.
+ *   - The settle record and the period record are records of one rule: with either tracking on
+ *     and turn > 0 any change of rule is GOLHIP_ERR_STATE (setting the rule the batch already has
+ *     is no change).  Change it at turn 0, i.e. after a load.
  *   - golhip_batch_get_rule with per-board rules set is GOLHIP_ERR_STATE; golhip_batch_get_rules
  *     always answers (the uniform rule repeated when no per-board rules are set).
  *   - B0 rules are allowed, as on the engine: the torus has no dead padding.

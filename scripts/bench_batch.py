@@ -27,6 +27,12 @@ also times the B3/S23 batch (gol_batch) of the same size and mode in the same pr
 the rule's call time over it ("vs_life").  --shapes / --batches narrow the run.  Without --rule the
 run and its output are what they always were.
 
+--period: the cost of period tracking (Batch.track_period, gol_batch_period) instead of the run
+above.  For every shape and B, plain and with history, the same process times the untracked call,
+the call with period tracking on and the call with settle tracking on (all under --rule, B3/S23
+without it) and reports period_ratio and settle_ratio: tracked call time over untracked.  The model
+for both is 3 more VALU per word per generation.  No engine yardstick in this leg.
+
 One JSON line on stdout; --out also writes it to a file.  There is no CPU fallback: without a GPU
 the script fails.
 """
@@ -59,6 +65,49 @@ def median_s(fn, warm, calls):
     return statistics.median(ts), min(ts)
 
 
+def period_leg(a, shapes, batches, rule, res):
+    """Untracked, period-tracked and settle-tracked calls of the same size, rule and mode, side by
+    side in this process."""
+    res["bench"] = "batch_period"
+    for w, h in shapes:
+        entry = {"width": w, "height": h, "batches": []}
+        for B in batches:
+            row = {"boards": B}
+            for mode in ("plain", "history"):
+                hist = mode == "history"
+                ms = {}
+                for track in ("none", "period", "settle"):
+                    with golhip.Batch(w, h, B) as b:
+                        b.init_random(seed0=1)
+                        if rule and a.per_board_rules:
+                            b.set_rules(np.tile(np.array(rule, dtype=np.uint32), (B, 1)))
+                        elif rule:
+                            b.set_rule(rule)
+                        if track == "period":
+                            b.track_period()
+                        elif track == "settle":
+                            b.track_settle()
+                        form = b.kernel_form
+                        med, best = median_s(lambda: b.step(TURNS, history=hist), 2, a.calls)
+                        if track == "period":
+                            repeats = int(np.count_nonzero(b.periods()[0] > 0))
+                    ms[track] = (med, best)
+                row[mode] = {"kernel_form": form, "boards_with_a_repeat": repeats,
+                             "call_ms_median": round(ms["none"][0] * 1e3, 3),
+                             "call_ms_min": round(ms["none"][1] * 1e3, 3),
+                             "period_call_ms_median": round(ms["period"][0] * 1e3, 3),
+                             "period_call_ms_min": round(ms["period"][1] * 1e3, 3),
+                             "settle_call_ms_median": round(ms["settle"][0] * 1e3, 3),
+                             "settle_call_ms_min": round(ms["settle"][1] * 1e3, 3),
+                             "gcups": round(B * w * h * TURNS / ms["none"][0] / 1e9, 2),
+                             "period_gcups": round(B * w * h * TURNS / ms["period"][0] / 1e9, 2),
+                             "period_ratio": round(ms["period"][0] / ms["none"][0], 3),
+                             "settle_ratio": round(ms["settle"][0] / ms["none"][0], 3)}
+            entry["batches"].append(row)
+            print(json.dumps({"shape": [w, h], **row}), file=sys.stderr, flush=True)
+        res["shapes"].append(entry)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=7)
@@ -69,6 +118,7 @@ def main():
     ap.add_argument("--per-board-rules", action="store_true")
     ap.add_argument("--shapes", help="e.g. 64x64,512x512 (default: all three)")
     ap.add_argument("--batches", help="e.g. 256,4096 (default: 1,256,4096,65536)")
+    ap.add_argument("--period", action="store_true", help="the cost of period tracking (see above)")
     a = ap.parse_args()
     assert a.calls >= 7
     assert a.rule or not a.per_board_rules, "--per-board-rules needs --rule"
@@ -83,6 +133,9 @@ def main():
     if rule:
         res["rule"] = golhip.rule_string(*rule)
         res["per_board_rules"] = a.per_board_rules
+    if a.period:
+        period_leg(a, shapes, batches if a.batches else [256, 4096], rule, res)
+        shapes = []  # this leg replaces the run below
     budget = 16 << 30  # bytes of boards plus their settle copy a batch may take here
     for w, h in shapes:
         cells = w * h
