@@ -21,14 +21,21 @@
 // excludes settle tracking (one tracker per launch keeps the kernel count down), and its record
 // too is the record of one rule.
 //
+// The soup search (golhip_batch_search) runs gol_batch_search (batch_search.hpp): soups are seeds, not
+// boards of the batch.  The handle lends its size, device, stream and uniform rule; its boards, turn,
+// records and switches are not touched.  Soups go out in chunks of at most kSearchChunk soups and
+// at most 2^44 cell updates, so that no launch runs long on a shared device.
+//
 // Device memory is allocated at create (the boards, the per-board counters, the transfer stage), by
 // the first golhip_batch_track_settle(b, 1) (board(t - 1) of every board), by the first
 // golhip_batch_track_period(b, 1) (every board's snapshot and its repeat turn) and by the first
-// golhip_batch_set_rules (the per-board rule pairs); no other call allocates.  Bytes in and out,
+// golhip_batch_set_rules (the per-board rule pairs) and by the first golhip_batch_search (one chunk's
+// seeds, rule pairs and records); no other call allocates.  Bytes in and out,
 // the seeds of init_random, per-board rules and counts and the per-turn history all pass through
 // the stage in chunks.
 #include <algorithm>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -58,11 +65,18 @@ struct golhip_batch {
     bool per_board = false;              // the boards run `rules`, not `rule`
     uint32_t *rules = nullptr;           // device: nboards (birth, survive) pairs
     std::vector<uint32_t> rules_host;    // the same pairs, for golhip_batch_get_rules
+    // golhip_batch_search: one chunk's seeds, rule pairs and records
+    uint64_t *search_seeds = nullptr;
+    uint32_t *search_rules = nullptr;
+    golhip::SoupRecord *search_out = nullptr;
     std::string err;
 };
 
 namespace golhip {
 namespace {
+
+constexpr int64_t kSearchChunk = 65536;                     // soups per gol_batch_search launch, at most
+constexpr int64_t kSearchChunkUpdates = (int64_t)1 << 44;  // cell updates per launch if no soup repeats, at most
 
 int bfail(golhip_batch_t b, int code, const char *fmt, ...) {
     char buf[512];
@@ -95,11 +109,17 @@ void batch_free(golhip_batch_t b) {
     if (b->repeat_turn) (void)hipFree(b->repeat_turn);
     if (b->stage) (void)hipFree(b->stage);
     if (b->rules) (void)hipFree(b->rules);
+    if (b->search_seeds) (void)hipFree(b->search_seeds);
+    if (b->search_rules) (void)hipFree(b->search_rules);
+    if (b->search_out) (void)hipFree(b->search_out);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     b->boards = b->prev = b->rules = b->snap = nullptr;
     b->last_diff = nullptr;
     b->repeat_turn = nullptr;
     b->stage = nullptr;
+    b->search_seeds = nullptr;
+    b->search_rules = nullptr;
+    b->search_out = nullptr;
     b->stream = nullptr;
 }
 
@@ -505,6 +525,72 @@ int golhip_batch_get_rules(golhip_batch_t b, uint32_t *birth, uint32_t *survive)
     for (int i = 0; i < b->nboards; ++i) {
         birth[i] = b->per_board ? b->rules_host[2 * (size_t)i] : b->rule.birth;
         survive[i] = b->per_board ? b->rules_host[2 * (size_t)i + 1] : b->rule.survive;
+    }
+    return GOLHIP_OK;
+}
+
+int golhip_batch_search(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds, uint64_t seed0, uint32_t density_q32,
+                        int64_t max_turns, const uint32_t *birth, const uint32_t *survive, golhip_soup_t *out) {
+    if (!b) return GOLHIP_ERR_ARG;
+    if (b->width % 64 != 0)
+        return bfail(b, GOLHIP_ERR_ARG, "search needs width %% 64 == 0, as init_random (width %lld)", (long long)b->width);
+    if (max_turns < 1 || max_turns > kSearchMaxTurns)
+        return bfail(b, GOLHIP_ERR_ARG, "search max_turns %lld: 1 to %lld", (long long)max_turns,
+                     (long long)kSearchMaxTurns);
+    if (nsoups < 0) return bfail(b, GOLHIP_ERR_ARG, "search nsoups %lld < 0", (long long)nsoups);
+    if (!birth != !survive) return bfail(b, GOLHIP_ERR_ARG, "birth and survive: both arrays, or both null");
+    if (birth) {
+        for (int64_t i = 0; i < nsoups; ++i) {
+            if ((birth[i] | survive[i]) & ~kRuleMaskBits)
+                return bfail(b, GOLHIP_ERR_ARG, "soup %lld: rule masks birth=0x%x survive=0x%x: bits above 8 (a cell "
+                             "has 8 neighbours)", (long long)i, birth[i], survive[i]);
+        }
+    }
+    if (nsoups == 0) return GOLHIP_OK;
+    if (!out) return bfail(b, GOLHIP_ERR_ARG, "out is null");
+    static_assert(sizeof(golhip_soup_t) == 32 && sizeof(SoupRecord) == 32, "a soup's record is 32 bytes");
+    static_assert(offsetof(golhip_soup_t, repeat_turn) == offsetof(SoupRecord, repeat_turn) &&
+                      offsetof(golhip_soup_t, period) == offsetof(SoupRecord, period) &&
+                      offsetof(golhip_soup_t, stop_turn) == offsetof(SoupRecord, stop_turn) &&
+                      offsetof(golhip_soup_t, population) == offsetof(SoupRecord, population) &&
+                      offsetof(golhip_soup_t, reserved) == offsetof(SoupRecord, reserved),
+                  "the kernel's record is golhip_soup_t");
+    BHIPCHK(b, hipSetDevice(b->device));
+    if (!b->search_seeds) BHIPCHK(b, hipMalloc(&b->search_seeds, sizeof(uint64_t) * (size_t)kSearchChunk));
+    if (!b->search_rules) BHIPCHK(b, hipMalloc(&b->search_rules, 2 * sizeof(uint32_t) * (size_t)kSearchChunk));
+    if (!b->search_out) BHIPCHK(b, hipMalloc(&b->search_out, sizeof(SoupRecord) * (size_t)kSearchChunk));
+    // a chunk: at most kSearchChunk soups and at most 2^44 cell updates if no soup repeats, at least 1
+    const int64_t chunk = std::max<int64_t>(
+        1, std::min<int64_t>(kSearchChunk, kSearchChunkUpdates / (b->width * b->height * max_turns)));
+    BatchSearchParams sp{};
+    sp.density = density_q32;
+    sp.wd = b->wd;
+    sp.width = (int32_t)b->width;
+    sp.max_turns = (int32_t)max_turns;
+    sp.rule = b->rule;  // the uniform rule; the handle's per-board rules belong to its boards
+    sp.rules = birth ? b->search_rules : nullptr;
+    sp.out = b->search_out;
+    std::vector<uint32_t> pairs;
+    for (int64_t i = 0; i < nsoups; i += chunk) {
+        const int64_t n = std::min(chunk, nsoups - i);
+        if (seeds) {
+            BHIPCHK(b, hipMemcpyAsync(b->search_seeds, seeds + i, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice,
+                                      b->stream));
+            sp.seeds = b->search_seeds;
+        } else {
+            sp.seed0 = seed0 + (uint64_t)i;
+        }
+        if (birth) {
+            pairs.resize(2 * (size_t)n);
+            for (int64_t j = 0; j < n; ++j) pairs[2 * j] = birth[i + j], pairs[2 * j + 1] = survive[i + j];
+            BHIPCHK(b, hipMemcpyAsync(b->search_rules, pairs.data(), 2 * sizeof(uint32_t) * (size_t)n,
+                                      hipMemcpyHostToDevice, b->stream));
+        }
+        // a missing kernel is an error
+        BHIPCHK(b, launch_batch_search(b->W, b->R, (int)n, sp, b->stream));
+        BHIPCHK(b, hipMemcpyAsync(out + i, b->search_out, sizeof(SoupRecord) * (size_t)n, hipMemcpyDeviceToHost,
+                                  b->stream));
+        BHIPCHK(b, hipStreamSynchronize(b->stream));  // the next chunk rewrites the buffers (and `pairs`)
     }
     return GOLHIP_OK;
 }

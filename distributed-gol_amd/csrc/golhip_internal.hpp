@@ -43,6 +43,32 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
     return z ^ (z >> 31);
 }
+// Word `col` (of the torus row's wd words) of row y of the random board of `seed` (width % 64 == 0):
+// what init_random_rows and batch_init_random store there, generated straight into registers by
+// gol_batch_search (batch_search.hpp).  density 0x80000000 takes 32 bits of one draw per 64 cells,
+// every other density compares one draw per cell.  The two init kernels keep the expression in
+// their own loops: calling this from batch_init_random changed batch_board.hip's code object
+// (another register assignment), and that object is held fixed;
+// tests/test_gpu_batch_search.py compares the soups with batch_init_random's boards.
+__device__ __forceinline__ uint32_t init_random_word(uint64_t seed, int64_t y, int32_t col, int64_t width,
+                                                     uint32_t density) {
+    const uint64_t g = 0x9E3779B97F4A7C15ULL;
+    const int64_t wpr = width / 64;
+    const int64_t x0 = ((int64_t)col * 32) % width;
+    uint32_t v = 0;
+    if (density == 0x80000000u) {
+        const uint64_t wi = (uint64_t)y * wpr + (uint64_t)(x0 >> 6);
+        const uint64_t wv = splitmix64(seed + (wi + 1) * g);
+        v = (x0 & 32) ? (uint32_t)(wv >> 32) : (uint32_t)wv;
+    } else {
+        for (int b = 0; b < 32; ++b) {
+            const uint64_t cell = (uint64_t)y * width + (uint64_t)(x0 + b);
+            const uint32_t d = (uint32_t)splitmix64(seed + (cell + 1) * g);
+            v |= (uint32_t)(d < density) << b;
+        }
+    }
+    return v;
+}
 
 struct StencilParams {
     int64_t pitch;       // words between consecutive rows
@@ -341,6 +367,33 @@ hipError_t launch_batch_period_life(int K, int W, int R, int nboards, const Batc
 #define GOLHIP_X(B, S)                                                                                        \
     hipError_t launch_batch_period_##B##_##S(int K, int W, int R, int nboards, const BatchPeriodParams &pp, \
                                              hipStream_t s);
+GOLHIP_RULE_CATALOGUE(GOLHIP_X)
+#undef GOLHIP_X
+// The soup search (gol_batch_search, batch_search.hpp; one translation unit per functor,
+// batch_search_*.hip): workgroup i generates the board of seed_i = seeds ? seeds[i] : seed0 + i in
+// registers (init_random_word), runs it from generation 0 under `rule` -- or, with rules != null,
+// under its own pair -- with gol_batch_period's cycle detection until it repeats or max_turns have
+// run, and writes out[i].  No board memory: a soup's footprint is its record.
+struct SoupRecord {  // golhip_soup_t (include/golhip.h)
+    int64_t repeat_turn, period, stop_turn;
+    uint32_t population, reserved;
+};
+constexpr int64_t kSearchMaxTurns = 1 << 20;
+struct BatchSearchParams {
+    const uint64_t *seeds;  // device memory, one per soup of the launch, or null
+    uint64_t seed0;
+    uint32_t density;  // q32
+    int32_t wd;        // words per torus row: 4, 8 or 16
+    int32_t width;     // cells per board row, a multiple of 64
+    int32_t max_turns;
+    RuleMasks rule;
+    const uint32_t *rules;  // device memory, one (birth, survive) pair per soup, or null
+    SoupRecord *out;
+};
+hipError_t launch_batch_search(int W, int R, int nsoups, const BatchSearchParams &sp, hipStream_t s);
+hipError_t launch_batch_search_life(int W, int R, int nsoups, const BatchSearchParams &sp, hipStream_t s);
+#define GOLHIP_X(B, S) \
+    hipError_t launch_batch_search_##B##_##S(int W, int R, int nsoups, const BatchSearchParams &sp, hipStream_t s);
 GOLHIP_RULE_CATALOGUE(GOLHIP_X)
 #undef GOLHIP_X
 // init_random_rows for every board: board i from seeds ? seeds[i] (device memory) : seed0 + i.

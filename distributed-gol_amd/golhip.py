@@ -62,7 +62,7 @@ EXPORTS = [
     "golhip_batch_track_settle", "golhip_batch_settled", "golhip_batch_turn",
     "golhip_batch_set_rule", "golhip_batch_set_rule_masks", "golhip_batch_get_rule", "golhip_batch_set_rules",
     "golhip_batch_get_rules", "golhip_batch_kernel",
-    "golhip_batch_track_period", "golhip_batch_periods",
+    "golhip_batch_track_period", "golhip_batch_periods", "golhip_batch_search",
 ]
 
 
@@ -70,6 +70,23 @@ class GolHipError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"golhip error {code}: {msg}")
         self.code = code
+
+
+class Soup(ctypes.Structure):
+    """golhip_soup_t: one soup's record of golhip_batch_search."""
+    _fields_ = [("repeat_turn", ctypes.c_int64), ("period", ctypes.c_int64), ("stop_turn", ctypes.c_int64),
+                ("population", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+SOUP_DTYPE = np.dtype([("repeat_turn", "<i8"), ("period", "<i8"), ("stop_turn", "<i8"), ("population", "<u4"),
+                       ("reserved", "<u4")])
+SEARCH_MAX_TURNS = 1 << 20
+
+
+def search_stop_turn(repeat_turn: int, max_turns: int) -> int:
+    """The generations Batch.search runs a soup whose first repeat is at turn repeat_turn (-1: none
+    within max_turns): max_turns, or min(max_turns, 32 * ((repeat_turn - 1) // 32) + 40)."""
+    return max_turns if repeat_turn < 0 else min(max_turns, 32 * ((repeat_turn - 1) // 32) + 40)
 
 
 class Xfer(ctypes.Structure):
@@ -249,6 +266,8 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
         "golhip_batch_settled": ([H, ctypes.c_void_p], i32),
         "golhip_batch_track_period": ([H, i32], i32),
         "golhip_batch_periods": ([H, ctypes.c_void_p, ctypes.c_void_p], i32),
+        "golhip_batch_search": ([H, i64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, i64, ctypes.c_void_p,
+                                 ctypes.c_void_p, ctypes.c_void_p], i32),
         "golhip_batch_turn": ([H, i64p], i32),
         "golhip_batch_set_rule": ([H, ctypes.c_char_p], i32),
         "golhip_batch_set_rule_masks": ([H, ctypes.c_uint32, ctypes.c_uint32], i32),
@@ -951,6 +970,38 @@ class Batch:
         period = np.zeros(self.nboards, dtype=np.int64)
         self._check(self._L.golhip_batch_periods(self._h, repeat_turn.ctypes.data, period.ctypes.data))
         return repeat_turn, period
+
+    def search(self, nsoups: int, *, seeds=None, seed0: int = 0, density_q32: int = DENSITY_HALF, max_turns: int,
+               rules=None) -> np.ndarray:
+        """A soup search on the device (golhip_batch_search): soup i is the board init_random gives
+        seed_i = seeds[i] (seed0 + i without seeds) at density_q32 on this batch's size; one
+        workgroup generates it in registers and runs it from generation 0 until it repeats or
+        max_turns (1 .. 2 ** 20) have run.  Returns a structured array (SOUP_DTYPE) of nsoups
+        records: repeat_turn and period as periods() defines them (-1, -1 without a repeat within
+        max_turns), stop_turn = search_stop_turn(repeat_turn, max_turns), the generations the soup
+        ran, population, its alive cells then, and reserved = 0.  A record depends on the soup's
+        seed, the density, the size, the rule and max_turns only.
+
+        The rule is the batch's uniform rule; rules (nsoups rule texts or (birth, survive) pairs,
+        checked as set_rules checks its own) gives every soup its own.  nsoups is independent of
+        nboards, and the batch's boards, turn, records and tracking switches are left as they were.
+        The workflow: search, pick the records of interest, then init_random(seeds=interesting) on
+        a batch of that many boards to look at the boards themselves."""
+        nsoups = int(nsoups)
+        sptr = bptr = vptr = None
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+            if seeds.shape != (max(nsoups, 0),):
+                raise GolHipError(ERR_ARG, f"seeds: shape {seeds.shape} for {nsoups} soups")
+            sptr = seeds.ctypes.data
+        if rules is not None:
+            pairs = self._pairs_of(rules, nsoups)
+            birth, survive = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+            bptr, vptr = birth.ctypes.data, survive.ctypes.data
+        out = np.zeros(max(nsoups, 0), dtype=SOUP_DTYPE)
+        self._check(self._L.golhip_batch_search(self._h, nsoups, sptr, seed0, density_q32, max_turns, bptr, vptr,
+                                                out.ctypes.data))
+        return out
 
     @property
     def turn(self) -> int:

@@ -416,7 +416,8 @@ int golhip_edge_wait(golhip_t h, double *total_ms, int64_t *blocks);
  *   - Board i of a load or store sits at cells + (i - first) * board_stride + y * row_stride; input
  *     0 / nonzero, output 0 / 255.  No call but create, the first golhip_batch_track_settle(b, 1), the
  *     first golhip_batch_track_period(b, 1) (a second boards-sized buffer, the snapshots, and one
- *     int64 per board) and the first golhip_batch_set_rules allocates device memory: bytes, seeds, rules, counts and
+ *     int64 per board), the first golhip_batch_set_rules and the first golhip_batch_search (one chunk's
+ *     seeds, rule pairs and records: 3 MiB) allocates device memory: bytes, seeds, rules, counts and
  *     history go through a transfer stage in chunks.
  *   - A batch has ONE turn counter.  Any golhip_batch_load_bytes, even of part of the batch, and any
  *     golhip_batch_init_random set it to 0 and clear every settle and period record: a batch is filled, then run.
@@ -496,6 +497,44 @@ int golhip_batch_get_rule(golhip_batch_t b, uint32_t *birth, uint32_t *survive);
 int golhip_batch_set_rules(golhip_batch_t b, const uint32_t *birth /* nboards */, const uint32_t *survive);
 int golhip_batch_get_rules(golhip_batch_t b, uint32_t *birth /* nboards */, uint32_t *survive);
 int golhip_batch_kernel(golhip_batch_t b, int *form);
+/* The soup search: a soup is a seed.  One workgroup (gol_batch_search) generates the board of soup i
+ * in registers -- bit for bit the board golhip_batch_init_random gives seed_i = seeds ? seeds[i] :
+ * seed0 + i at density_q32 -- and runs it from generation 0, with the cycle detection of the block
+ * above, until it repeats or max_turns have run; then the soup is retired and the workgroup ends.
+ * No board memory is read or written: the footprint of a soup is its 32-byte record, and nsoups has
+ * nothing to do with nboards.
+ *   - out[i] depends on soup i's seed, the density, the board size, the rule and max_turns only: not
+ *     on nsoups, the soup's position, the chunking or nboards.
+ *   - repeat_turn and period are exactly what golhip_batch_init_random with that seed,
+ *     golhip_batch_track_period, golhip_batch_step(max_turns) and golhip_batch_periods report; -1 and
+ *     -1 when the soup has no repeat within max_turns.
+ *   - stop_turn, the generations the soup ran, is a function of (repeat_turn, max_turns): max_turns
+ *     when there is no repeat, else min(max_turns, 32 * ((repeat_turn - 1) / 32) + 40) (integer
+ *     division): the kernel learns of a repeat once per 32 generations and every wave of the
+ *     workgroup leaves 8 generations later, between repeat_turn + 8 and repeat_turn + 39.
+ *   - population is the alive count of the soup at stop_turn; reserved is 0.
+ *   - The handle gives the size, the device, the stream and the UNIFORM rule (golhip_batch_set_rule;
+ *     B3/S23 runs LifeNext, a catalogue rule its constant-folded kernel, any other rule the table
+ *     form).  The handle's per-board rules belong to its boards and do not apply to soups.  birth and
+ *     survive, both given or both NULL, are nsoups masks each: soup i runs its own rule (the table
+ *     form).  The search leaves the batch's boards, turn, settle and period records and switches
+ *     exactly as they were.  To look at a soup, golhip_batch_init_random with its seed.
+ *   - GOLHIP_ERR_ARG: width % 64 != 0 (as init_random); max_turns outside 1..2^20; nsoups < 0; a mask
+ *     with bits above 8 (golhip_batch_last_error names the soup index and the mask); exactly one of
+ *     birth and survive; out == NULL with nsoups > 0.  The handle and out are then untouched.
+ *     nsoups == 0 is a no-op.
+ *   - Soups are launched in chunks of at most 65536 soups and at most 2^44 cell updates (chunk *
+ *     width * height * max_turns; never fewer than 1 soup), so that no launch runs long.  The first
+ *     search allocates the device buffers of one chunk (seeds, rule pairs, records);
+ *     golhip_batch_destroy frees them. */
+typedef struct {
+    int64_t repeat_turn, period, stop_turn;
+    uint32_t population, reserved;
+} golhip_soup_t;
+int golhip_batch_search(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds /* nsoups, or NULL */,
+                        uint64_t seed0, uint32_t density_q32, int64_t max_turns,
+                        const uint32_t *birth /* nsoups, or NULL */, const uint32_t *survive,
+                        golhip_soup_t *out /* nsoups */);
 
 #ifdef __cplusplus
 }

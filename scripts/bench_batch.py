@@ -33,6 +33,14 @@ the call with period tracking on and the call with settle tracking on (all under
 without it) and reports period_ratio and settle_ratio: tracked call time over untracked.  The model
 for both is 3 more VALU per word per generation.  No engine yardstick in this leg.
 
+--search: the soup search (Batch.search, gol_batch_search) against the only route there was before
+it, instead of the run above.  The same soups (seeds 0 .. --soups - 1 at density 1/2), rule and
+max_turns on both routes: (a) Batch(w, h, 4096) and per 4096 soups init_random(seeds), track_period,
+step(max_turns), periods(); (b) one Batch.search call.  The records (repeat_turn, period) must agree
+before anything is timed.  Reported: soups per second of both, their ratio, the mean stop_turn of
+the search and the soups that repeated.  The cases: 64 x 64 and 512 x 512 under B3/S23, 64 x 64 under
+HighLife and under B38/S0236 (where no soup repeats); max_turns 16384 at 64 x 64, 4096 at 512 x 512.
+
 One JSON line on stdout; --out also writes it to a file.  There is no CPU fallback: without a GPU
 the script fails.
 """
@@ -108,6 +116,57 @@ def period_leg(a, shapes, batches, rule, res):
         res["shapes"].append(entry)
 
 
+SEARCH_CASES = [(64, 64, "B3/S23", 16384), (512, 512, "B3/S23", 4096), (64, 64, "B36/S23", 16384),
+                (64, 64, "B38/S0236", 16384)]
+SEARCH_BATCH = 4096
+
+
+def search_leg(a, res):
+    """The step route and the search on the same soups, rule and max_turns, side by side in this
+    process."""
+    res["bench"] = "batch_search"
+    res["soups"] = a.soups
+    del res["turns"]
+    assert a.soups >= 1 and a.soups % SEARCH_BATCH == 0, "--soups: a multiple of 4096"
+    seeds = np.arange(a.soups, dtype=np.uint64)
+    for w, h, rule, max_turns in SEARCH_CASES:
+        if a.shapes and (w, h) not in [tuple(int(v) for v in t.split("x")) for t in a.shapes.split(",")]:
+            continue
+        with golhip.Batch(w, h, SEARCH_BATCH, rule=rule) as b:
+            form = b.kernel_form
+
+            def step_route():
+                turns, periods = [], []
+                for i in range(0, a.soups, SEARCH_BATCH):
+                    b.init_random(seeds=seeds[i:i + SEARCH_BATCH])
+                    b.track_period()
+                    b.step(max_turns)
+                    t, p = b.periods()
+                    turns.append(t)
+                    periods.append(p)
+                return np.concatenate(turns), np.concatenate(periods)
+
+            def search():
+                return b.search(a.soups, seeds=seeds, max_turns=max_turns)
+
+            turns, periods = step_route()
+            got = search()
+            assert np.array_equal(got["repeat_turn"], turns) and np.array_equal(got["period"], periods), (w, h, rule)
+            step_med, step_min = median_s(step_route, 2, a.calls)
+            search_med, search_min = median_s(search, 2, a.calls)
+        row = {"width": w, "height": h, "rule": rule, "kernel_form": form, "max_turns": max_turns,
+               "soups_with_a_repeat": int(np.count_nonzero(turns > 0)),
+               "mean_repeat_turn": round(float(turns[turns > 0].mean()), 1) if (turns > 0).any() else None,
+               "mean_stop_turn": round(float(got["stop_turn"].mean()), 1),
+               "step_route_ms_median": round(step_med * 1e3, 3), "step_route_ms_min": round(step_min * 1e3, 3),
+               "search_ms_median": round(search_med * 1e3, 3), "search_ms_min": round(search_min * 1e3, 3),
+               "step_route_soups_per_s": round(a.soups / step_med, 1),
+               "search_soups_per_s": round(a.soups / search_med, 1),
+               "search_over_step_route": round(step_med / search_med, 3)}
+        res["shapes"].append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=7)
@@ -119,6 +178,8 @@ def main():
     ap.add_argument("--shapes", help="e.g. 64x64,512x512 (default: all three)")
     ap.add_argument("--batches", help="e.g. 256,4096 (default: 1,256,4096,65536)")
     ap.add_argument("--period", action="store_true", help="the cost of period tracking (see above)")
+    ap.add_argument("--search", action="store_true", help="the soup search against the step route (see above)")
+    ap.add_argument("--soups", type=int, default=4096, help="--search: soups per call, a multiple of 4096")
     a = ap.parse_args()
     assert a.calls >= 7
     assert a.rule or not a.per_board_rules, "--per-board-rules needs --rule"
@@ -133,6 +194,10 @@ def main():
     if rule:
         res["rule"] = golhip.rule_string(*rule)
         res["per_board_rules"] = a.per_board_rules
+    if a.search:
+        assert not (a.rule or a.period), "--search has its own rules and replaces the other legs"
+        search_leg(a, res)
+        shapes = []  # this leg replaces the run below
     if a.period:
         period_leg(a, shapes, batches if a.batches else [256, 4096], rule, res)
         shapes = []  # this leg replaces the run below
