@@ -69,6 +69,8 @@ struct golhip_batch {
     uint64_t *search_seeds = nullptr;
     uint32_t *search_rules = nullptr;
     golhip::SoupRecord *search_out = nullptr;
+    int topology = GOLHIP_TOPOLOGY_TORUS;
+    int box_w = 0, box_h = 0;  // the soup box of init_random and search; 0, 0: the whole board
     std::string err;
 };
 
@@ -196,11 +198,19 @@ int transfer(golhip_batch_t b, int first, int n, uint8_t *host, size_t row_strid
 }
 
 // What the next step launches: 0 gol_batch (uniform B3/S23), 1 gol_batch_rule constant-folded, 2 its
-// table form, 3 the table form with per-board rules.
+// table form, 3 the table form with per-board rules.  On a plane: 0 B3/S23's rule step, 2 the table
+// form for every other uniform rule (the plane has no constant-folded kernels), 3 per-board rules.
 int kernel_form(const golhip_batch *b) {
     if (b->per_board) return 3;
     if (b->rule.birth == kLifeBirth && b->rule.survive == kLifeSurvive) return 0;
+    if (b->topology == GOLHIP_TOPOLOGY_PLANE) return 2;
     return rule_catalogued(b->rule.birth, b->rule.survive) ? 1 : 2;
+}
+
+// The soup box in cells: centred, the whole board when none is set.
+SoupBox soup_box(const golhip_batch *b) {
+    if (b->box_w == 0) return SoupBox{0, 0, (int32_t)b->width, (int32_t)b->height};
+    return SoupBox{(int32_t)((b->width - b->box_w) / 2), (int32_t)((b->height - b->box_h) / 2), b->box_w, b->box_h};
 }
 
 // The settle record (last_diff, prev) and the period record (repeat_turn, snap) describe the boards
@@ -287,6 +297,9 @@ int golhip_batch_init_random(golhip_batch_t b, const uint64_t *seeds, uint64_t s
     if (!seeds) {
         BHIPCHK(b, launch_batch_init_random(b->boards, b->board_words, b->nboards, b->height, b->width, b->wd,
                                             nullptr, seed0, density_q32, b->stream));
+        if (b->box_w)  // the boxed soup: the full-board soup with the cells outside the box cleared
+            BHIPCHK(b, launch_batch_clip_box(b->boards, b->board_words, b->nboards, b->height, b->width, b->wd,
+                                             soup_box(b), b->stream));
     } else {  // the seeds through the stage, a chunk of boards at a time
         uint64_t *dseeds = reinterpret_cast<uint64_t *>(b->stage);
         const int64_t cb = std::max<int64_t>(1, b->stage_bytes / (int64_t)sizeof(uint64_t));
@@ -296,6 +309,9 @@ int golhip_batch_init_random(golhip_batch_t b, const uint64_t *seeds, uint64_t s
                                       b->stream));
             BHIPCHK(b, launch_batch_init_random(b->boards + i * b->board_words, b->board_words, nb, b->height,
                                                 b->width, b->wd, dseeds, 0, density_q32, b->stream));
+            if (b->box_w)
+                BHIPCHK(b, launch_batch_clip_box(b->boards + i * b->board_words, b->board_words, nb, b->height,
+                                                 b->width, b->wd, soup_box(b), b->stream));
             BHIPCHK(b, hipStreamSynchronize(b->stream));
         }
     }
@@ -325,10 +341,17 @@ int golhip_batch_step(golhip_batch_t b, int64_t turns, uint32_t *history, size_t
     p.prev = b->track ? b->prev : nullptr;
     p.last_diff = b->track ? b->last_diff : nullptr;
     const int form = kernel_form(b);
+    const bool plane = b->topology == GOLHIP_TOPOLOGY_PLANE;
     for (int64_t done = 0; done < turns;) {
         const int K = (int)std::min<int64_t>(kmax, turns - done);
         p.t0 = b->turn;
-        if (b->track_period) {  // every rule form, B3/S23 included: the period kernels
+        if (plane && b->track_period) {  // the plane kernels: every rule form, B3/S23 included
+            const BatchPeriodParams pp{p, b->rule, b->per_board ? b->rules : nullptr, b->snap, b->repeat_turn};
+            BHIPCHK(b, launch_plane_period(K, b->W, b->R, b->nboards, pp, b->stream));
+        } else if (plane) {
+            const BatchRuleParams rp{p, b->rule, b->per_board ? b->rules : nullptr};
+            BHIPCHK(b, launch_plane_rule(K, b->W, b->R, b->nboards, rp, b->stream));
+        } else if (b->track_period) {  // every rule form, B3/S23 included: the period kernels
             const BatchPeriodParams pp{p, b->rule, b->per_board ? b->rules : nullptr, b->snap, b->repeat_turn};
             BHIPCHK(b, launch_batch_period(K, b->W, b->R, b->nboards, pp, b->stream));
         } else if (form == 0) {
@@ -570,6 +593,9 @@ int golhip_batch_search(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds,
     sp.rule = b->rule;  // the uniform rule; the handle's per-board rules belong to its boards
     sp.rules = birth ? b->search_rules : nullptr;
     sp.out = b->search_out;
+    // the plane, or a box on either topology: gol_plane_search; a torus of whole-board soups runs
+    // gol_batch_search as before
+    const bool boxed = b->topology == GOLHIP_TOPOLOGY_PLANE || b->box_w != 0;
     std::vector<uint32_t> pairs;
     for (int64_t i = 0; i < nsoups; i += chunk) {
         const int64_t n = std::min(chunk, nsoups - i);
@@ -587,11 +613,56 @@ int golhip_batch_search(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds,
                                       hipMemcpyHostToDevice, b->stream));
         }
         // a missing kernel is an error
-        BHIPCHK(b, launch_batch_search(b->W, b->R, (int)n, sp, b->stream));
+        if (boxed) {
+            const BatchBoxSearchParams bp{sp, soup_box(b), b->topology == GOLHIP_TOPOLOGY_PLANE ? 1 : 0};
+            BHIPCHK(b, launch_plane_search(b->W, b->R, (int)n, bp, b->stream));
+        } else {
+            BHIPCHK(b, launch_batch_search(b->W, b->R, (int)n, sp, b->stream));
+        }
         BHIPCHK(b, hipMemcpyAsync(out + i, b->search_out, sizeof(SoupRecord) * (size_t)n, hipMemcpyDeviceToHost,
                                   b->stream));
         BHIPCHK(b, hipStreamSynchronize(b->stream));  // the next chunk rewrites the buffers (and `pairs`)
     }
+    return GOLHIP_OK;
+}
+
+int golhip_batch_set_topology(golhip_batch_t b, int topology) {
+    if (!b) return GOLHIP_ERR_ARG;
+    if (topology != GOLHIP_TOPOLOGY_TORUS && topology != GOLHIP_TOPOLOGY_PLANE)
+        return bfail(b, GOLHIP_ERR_ARG, "topology %d: 0 (a torus) or 1 (a plane)", topology);
+    if (topology == b->topology) return GOLHIP_OK;
+    // the settle and period records describe the boards under one rule on one topology
+    if (b->track && b->turn > 0)
+        return bfail(b, GOLHIP_ERR_STATE, "settle tracking is on at turn %lld: the settle record holds on one topology, "
+                     "change it at turn 0 (after a load)", (long long)b->turn);
+    if (b->track_period && b->turn > 0)
+        return bfail(b, GOLHIP_ERR_STATE, "period tracking is on at turn %lld: a repeat means a cycle on one topology "
+                     "only, change it at turn 0 (after a load)", (long long)b->turn);
+    b->topology = topology;
+    return GOLHIP_OK;
+}
+
+int golhip_batch_get_topology(golhip_batch_t b, int *topology) {
+    if (!b || !topology) return GOLHIP_ERR_ARG;
+    *topology = b->topology;
+    return GOLHIP_OK;
+}
+
+int golhip_batch_set_soup_box(golhip_batch_t b, int box_w, int box_h) {
+    if (!b) return GOLHIP_ERR_ARG;
+    const bool off = box_w == 0 && box_h == 0;
+    if (!off && (box_w < 1 || box_w > b->width || box_h < 1 || box_h > b->height))
+        return bfail(b, GOLHIP_ERR_ARG, "soup box %d x %d: 1..%lld by 1..%lld cells, or 0, 0 for the whole board", box_w,
+                     box_h, (long long)b->width, (long long)b->height);
+    b->box_w = box_w;
+    b->box_h = box_h;
+    return GOLHIP_OK;
+}
+
+int golhip_batch_get_soup_box(golhip_batch_t b, int *box_w, int *box_h) {
+    if (!b || !box_w || !box_h) return GOLHIP_ERR_ARG;
+    *box_w = b->box_w;
+    *box_h = b->box_h;
     return GOLHIP_OK;
 }
 

@@ -396,6 +396,40 @@ hipError_t launch_batch_search_life(int W, int R, int nsoups, const BatchSearchP
     hipError_t launch_batch_search_##B##_##S(int W, int R, int nsoups, const BatchSearchParams &sp, hipStream_t s);
 GOLHIP_RULE_CATALOGUE(GOLHIP_X)
 #undef GOLHIP_X
+// The batch kernels on a bounded plane (batch_plane.hpp; translation units batch_plane_*.hip): the
+// contracts of launch_batch_rule (uniform B3/S23 included, which runs gol_batch's rule step),
+// launch_batch_period and launch_batch_search with every neighbour outside the width x height
+// rectangle dead.  Two functors: B3/S23's rule step for a uniform B3/S23, the table form for every
+// other rule and for per-board rules.  The torus launches above never reach these.
+hipError_t launch_plane_rule(int K, int W, int R, int nboards, const BatchRuleParams &rp, hipStream_t s);
+hipError_t launch_plane_rule_life(int K, int W, int R, int nboards, const BatchRuleParams &rp, hipStream_t s);
+hipError_t launch_plane_period(int K, int W, int R, int nboards, const BatchPeriodParams &pp, hipStream_t s);
+hipError_t launch_plane_period_life(int K, int W, int R, int nboards, const BatchPeriodParams &pp, hipStream_t s);
+// The soup box: cells outside columns [x0, x0 + w) and rows [y0, y0 + h) of a soup are cleared.
+struct SoupBox {
+    int32_t x0, y0, w, h;
+};
+// The bits of word `col` (of wd words) of row y whose cells lie in the box; width % 32 == 0.
+__device__ __forceinline__ uint32_t box_word_mask(int64_t y, int32_t col, int32_t width, const SoupBox &bx) {
+    if (y < bx.y0 || y >= (int64_t)bx.y0 + bx.h) return 0u;
+    const int32_t x0 = (col * 32) % width;
+    const int32_t lo = min(max(bx.x0 - x0, 0), 32), hi = min(max(bx.x0 + bx.w - x0, 0), 32);
+    if (hi <= lo) return 0u;
+    const uint32_t below_hi = hi == 32 ? ~0u : (1u << hi) - 1u;
+    return below_hi & ~((1u << lo) - 1u);  // lo < hi <= 32
+}
+// A search on the plane, or a boxed search on either topology (plane == 0: the torus, which only a
+// box brings here): BatchSearchParams with the box (the whole board: no box) applied at seeding.
+struct BatchBoxSearchParams {
+    BatchSearchParams s;
+    SoupBox box;
+    int32_t plane;
+};
+hipError_t launch_plane_search(int W, int R, int nsoups, const BatchBoxSearchParams &bp, hipStream_t s);
+hipError_t launch_plane_search_life(int W, int R, int nsoups, const BatchBoxSearchParams &bp, hipStream_t s);
+// Clears every cell outside the box in boards of the batch layout (after launch_batch_init_random).
+hipError_t launch_batch_clip_box(uint32_t *boards, int64_t board_pitch, int64_t nboards, int64_t rows, int64_t width,
+                                 int32_t wd, const SoupBox &box, hipStream_t s);
 // init_random_rows for every board: board i from seeds ? seeds[i] (device memory) : seed0 + i.
 hipError_t launch_batch_init_random(uint32_t *boards, int64_t board_pitch, int64_t nboards, int64_t rows,
                                     int64_t width, int32_t wd, const uint64_t *seeds, uint64_t seed0,

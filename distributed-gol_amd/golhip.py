@@ -36,6 +36,8 @@ NCCL_ID_BYTES = 128
 DENSITY_HALF = 0x80000000
 HANDOFF_FENCED, HANDOFF_SC1 = 0, 1  # golhip_set_persistent_handoff
 RECT_COPY, RECT_OR, RECT_XOR = 0, 1, 2  # golhip_load_rect
+TOPOLOGY_TORUS, TOPOLOGY_PLANE = 0, 1  # golhip_batch_set_topology
+_TOPOLOGIES = {"torus": TOPOLOGY_TORUS, "plane": TOPOLOGY_PLANE}
 _RECT_MODES = {"copy": RECT_COPY, "or": RECT_OR, "xor": RECT_XOR}
 
 # Every symbol include/golhip.h declares (tests/test_boundary.py checks the .so exports them).
@@ -63,6 +65,7 @@ EXPORTS = [
     "golhip_batch_set_rule", "golhip_batch_set_rule_masks", "golhip_batch_get_rule", "golhip_batch_set_rules",
     "golhip_batch_get_rules", "golhip_batch_kernel",
     "golhip_batch_track_period", "golhip_batch_periods", "golhip_batch_search",
+    "golhip_batch_set_topology", "golhip_batch_get_topology", "golhip_batch_set_soup_box", "golhip_batch_get_soup_box",
 ]
 
 
@@ -275,6 +278,10 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
         "golhip_batch_set_rules": ([H, ctypes.c_void_p, ctypes.c_void_p], i32),
         "golhip_batch_get_rules": ([H, ctypes.c_void_p, ctypes.c_void_p], i32),
         "golhip_batch_kernel": ([H, ctypes.POINTER(i32)], i32),
+        "golhip_batch_set_topology": ([H, i32], i32),
+        "golhip_batch_get_topology": ([H, ctypes.POINTER(i32)], i32),
+        "golhip_batch_set_soup_box": ([H, i32, i32], i32),
+        "golhip_batch_get_soup_box": ([H, ctypes.POINTER(i32), ctypes.POINTER(i32)], i32),
         "golhip_launch_kind_counts": ([H, i32, i32, ctypes.POINTER(ctypes.c_int),
                                        ctypes.POINTER(ctypes.c_int)], i32),
     }
@@ -832,14 +839,20 @@ class Batch:
     uniform B3/S23 runs gol_batch; any other rule runs gol_batch_rule, constant-folded for a uniform
     catalogue rule, in the table form otherwise -- per-board rules always (kernel_form).  Rule texts
     and the length of `rules` are checked before the handle is created: a bad one raises
-    GolHipError(ERR_ARG) naming it, without touching a device."""
+    GolHipError(ERR_ARG) naming it, without touching a device.
+
+    topology: "torus" (the default) or "plane", a bounded grid whose outside is dead (set_topology,
+    topology).  soup_box: (w, h), the centred box outside which init_random and search clear every
+    cell of a soup, or None for the whole board (set_soup_box, soup_box)."""
 
     def __init__(self, width: int, height: int, nboards: int, device: int = 0, *,
-                 rule: str | tuple[int, int] | None = None, rules=None, lib: ctypes.CDLL | None = None):
+                 rule: str | tuple[int, int] | None = None, rules=None, topology: str | int = "torus",
+                 soup_box: tuple[int, int] | None = None, lib: ctypes.CDLL | None = None):
         self._L = lib if lib is not None else load_library()
         self._h = ctypes.c_void_p()
         masks = None if rule is None else self._masks_of(rule)
         pairs = None if rules is None else self._pairs_of(rules, int(nboards))
+        topo = self._topology_of(topology)
         rc = self._L.golhip_batch_create(width, height, nboards, device, ctypes.byref(self._h))
         if rc != OK:
             why = self._L.golhip_batch_last_error(None).decode() or self._L.golhip_strerror(rc).decode()
@@ -849,6 +862,23 @@ class Batch:
             self.set_rule(masks)
         if pairs is not None:
             self.set_rules(pairs)
+        try:
+            if topo != TOPOLOGY_TORUS:
+                self.set_topology(topo)
+            if soup_box is not None:
+                self.set_soup_box(soup_box)
+        except GolHipError:
+            self.close()
+            raise
+
+    @staticmethod
+    def _topology_of(topology) -> int:
+        """The C value of "torus" / "plane"; an integer passes through for the library to check."""
+        if isinstance(topology, str):
+            if topology not in _TOPOLOGIES:
+                raise GolHipError(ERR_ARG, f"topology {topology!r}: \"torus\" or \"plane\"")
+            return _TOPOLOGIES[topology]
+        return int(topology)
 
     def _masks_of(self, rule, where: str = "") -> tuple[int, int]:
         """(birth, survive) of a rule text or a pair of masks; GolHipError(ERR_ARG) naming a bad one."""
@@ -909,7 +939,8 @@ class Batch:
 
     def init_random(self, seeds=None, seed0: int = 0, density_q32: int = DENSITY_HALF):
         """Board i as Engine.init_random(seed_i, density_q32) of a single engine of this size,
-        seed_i = seeds[i] if seeds is given, else seed0 + i."""
+        seed_i = seeds[i] if seeds is given, else seed0 + i; with a soup_box set, every cell outside
+        the box cleared."""
         ptr = None
         if seeds is not None:
             seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
@@ -980,7 +1011,10 @@ class Batch:
         records: repeat_turn and period as periods() defines them (-1, -1 without a repeat within
         max_turns), stop_turn = search_stop_turn(repeat_turn, max_turns), the generations the soup
         ran, population, its alive cells then, and reserved = 0.  A record depends on the soup's
-        seed, the density, the size, the rule and max_turns only.
+        seed, the density, the size, the rule, max_turns, the topology and the soup_box only: the
+        soup runs on the batch's topology ("plane": the outside is dead, a glider ends at the border
+        instead of circling the board), and with a soup_box set the soup is the seed's board with
+        every cell outside the centred box cleared, exactly what init_random then gives.
 
         The rule is the batch's uniform rule; rules (nsoups rule texts or (birth, survive) pairs,
         checked as set_rules checks its own) gives every soup its own.  nsoups is independent of
@@ -1008,6 +1042,35 @@ class Batch:
         v = ctypes.c_int64()
         self._check(self._L.golhip_batch_turn(self._h, ctypes.byref(v)))
         return v.value
+
+    # -- topology and the soup box
+    def set_topology(self, topology: str | int):
+        """"torus" or "plane" (golhip_batch_set_topology).  On a plane every neighbour outside the
+        width x height rectangle is dead.  Keeps the boards, the turn, the rules and the switches;
+        with settle or period tracking on, only at turn 0.  On a plane kernel_form is 0 for B3/S23, 2
+        for every other uniform rule, 3 for per-board rules."""
+        self._check(self._L.golhip_batch_set_topology(self._h, self._topology_of(topology)))
+
+    @property
+    def topology(self) -> str:
+        """"torus" or "plane"."""
+        v = ctypes.c_int32()
+        self._check(self._L.golhip_batch_get_topology(self._h, ctypes.byref(v)))
+        return "plane" if v.value == TOPOLOGY_PLANE else "torus"
+
+    def set_soup_box(self, box: tuple[int, int] | None):
+        """(w, h) with 1 <= w <= width and 1 <= h <= height, or None / (0, 0) for the whole board
+        (golhip_batch_set_soup_box).  The box sits at ((width - w) // 2, (height - h) // 2);
+        init_random and search clear every cell of a soup outside it, load ignores it."""
+        w, h = (0, 0) if box is None else (int(v) for v in box)
+        self._check(self._L.golhip_batch_set_soup_box(self._h, w, h))
+
+    @property
+    def soup_box(self) -> tuple[int, int] | None:
+        """The soup box (w, h), None for the whole board."""
+        w, h = ctypes.c_int32(), ctypes.c_int32()
+        self._check(self._L.golhip_batch_get_soup_box(self._h, ctypes.byref(w), ctypes.byref(h)))
+        return None if (w.value, h.value) == (0, 0) else (w.value, h.value)
 
     # -- the rule
     def set_rule(self, rule: str | tuple[int, int]):
@@ -1054,7 +1117,8 @@ class Batch:
     @property
     def kernel_form(self) -> int:
         """What the next step launches: 0 gol_batch (B3/S23), 1 gol_batch_rule constant-folded, 2 its
-        table form, 3 the table form with per-board rules."""
+        table form, 3 the table form with per-board rules.  On a plane: 0, 2 or 3 (no constant-folded
+        kernels there)."""
         v = ctypes.c_int32()
         self._check(self._L.golhip_batch_kernel(self._h, ctypes.byref(v)))
         return v.value

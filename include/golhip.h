@@ -503,8 +503,9 @@ int golhip_batch_kernel(golhip_batch_t b, int *form);
  * above, until it repeats or max_turns have run; then the soup is retired and the workgroup ends.
  * No board memory is read or written: the footprint of a soup is its 32-byte record, and nsoups has
  * nothing to do with nboards.
- *   - out[i] depends on soup i's seed, the density, the board size, the rule and max_turns only: not
- *     on nsoups, the soup's position, the chunking or nboards.
+ *   - out[i] depends on soup i's seed, the density, the board size, the rule, max_turns, the
+ *     topology and the soup box (the block below) only: not on nsoups, the soup's position, the
+ *     chunking or nboards.
  *   - repeat_turn and period are exactly what golhip_batch_init_random with that seed,
  *     golhip_batch_track_period, golhip_batch_step(max_turns) and golhip_batch_periods report; -1 and
  *     -1 when the soup has no repeat within max_turns.
@@ -535,6 +536,44 @@ int golhip_batch_search(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds 
                         uint64_t seed0, uint32_t density_q32, int64_t max_turns,
                         const uint32_t *birth /* nsoups, or NULL */, const uint32_t *survive,
                         golhip_soup_t *out /* nsoups */);
+/* Topology and the soup box: the standard search setting, a small random box in empty space on a
+ * bounded grid whose outside is dead (Golly's :P64,64 where the torus is :T64,64).
+ *   - A batch starts as a torus.  On GOLHIP_TOPOLOGY_PLANE the board is the same width x height
+ *     cells, every neighbour outside the rectangle counts as dead and no cell outside is ever alive:
+ *     under a B0 rule the cells inside are born as the rule says and the outside stays dead.  A
+ *     glider that leaves the ash does not circle the board: it ends as a block at the border, so a
+ *     lone glider on a 16 x 16 plane is (repeat_turn, period) = (64, 1) where the torus gives
+ *     (127, 64), and a period above 2 on a plane always means an oscillator.
+ *   - The plane runs every width and height a batch accepts, uniform and per-board rules, history,
+ *     settle tracking, period tracking and golhip_batch_search.  Every definition above (settled,
+ *     repeat_turn, period, stop_turn, population) holds word for word with "the board" stepped as a
+ *     plane.
+ *   - The plane has its own kernels (gol_plane_rule, gol_plane_period, gol_plane_search) in two
+ *     forms: B3/S23's rule step for a uniform B3/S23 and the table form for everything else.  It has
+ *     no constant-folded catalogue kernels: HighLife on a plane runs the table form.
+ *     golhip_batch_kernel on a plane reports 0 for a uniform B3/S23, 2 for every other uniform rule
+ *     and 3 for per-board rules.  A torus batch launches exactly what it launched before.
+ *   - golhip_batch_set_topology keeps the boards, the turn, the rules and the switches.  It follows
+ *     the rule-change contract: with settle or period tracking on and turn > 0 a change is
+ *     GOLHIP_ERR_STATE (setting the current value is no change); change it at turn 0, i.e. after a
+ *     load.  Any other value is GOLHIP_ERR_ARG and leaves the handle untouched.
+ *     golhip_batch_load_bytes, golhip_batch_init_random and golhip_batch_store_bytes do not touch
+ *     the topology.
+ *   - The soup box: golhip_batch_set_soup_box(b, box_w, box_h) with 1 <= box_w <= width and 1 <=
+ *     box_h <= height; (0, 0), the default, is the whole board; anything else is GOLHIP_ERR_ARG and
+ *     leaves the handle untouched.  The box sits at x0 = (width - box_w) / 2, y0 = (height -
+ *     box_h) / 2 (integer division).  The boxed soup of a seed is the full-board soup of that seed,
+ *     for either density path, with every cell outside the box cleared: seeds keep their meaning.
+ *     golhip_batch_init_random and golhip_batch_search both honour it, on either topology, so
+ *     "search, then init_random with the seeds of interest" still shows the boards that were
+ *     searched; golhip_batch_load_bytes ignores it.  A boxed search on the torus runs
+ *     gol_plane_search with its seams switched off (B3/S23's rule step or the table form). */
+#define GOLHIP_TOPOLOGY_TORUS 0
+#define GOLHIP_TOPOLOGY_PLANE 1
+int golhip_batch_set_topology(golhip_batch_t b, int topology);
+int golhip_batch_get_topology(golhip_batch_t b, int *topology);
+int golhip_batch_set_soup_box(golhip_batch_t b, int box_w, int box_h); /* 0, 0: the whole board (default) */
+int golhip_batch_get_soup_box(golhip_batch_t b, int *box_w, int *box_h);
 
 #ifdef __cplusplus
 }

@@ -41,6 +41,16 @@ before anything is timed.  Reported: soups per second of both, their ratio, the 
 the search and the soups that repeated.  The cases: 64 x 64 and 512 x 512 under B3/S23, 64 x 64 under
 HighLife and under B38/S0236 (where no soup repeats); max_turns 16384 at 64 x 64, 4096 at 512 x 512.
 
+--plane: the bounded plane (Batch(topology="plane"): gol_plane_rule / _period / _search) beside the
+torus, instead of the run above: --search's soups, rules and method, both topologies in this
+process.  Per case and topology: the step route over the first 4096 soups (init_random(seeds),
+track_period, step(max_turns), periods()) and one Batch.search call of --soups soups; the plane's
+search records (repeat_turn, period) of the first 4096 soups must equal the plane step route's
+before anything is timed.  Reported: call times, soups per second and plane / torus ratios of both
+routes.  The cases: 64 x 64 and 512 x 512 under B3/S23 and under B38/S0236 (the table form);
+--max-turns overrides their max_turns.  --box WxH adds the soup box to every batch of this leg
+(the boxed search: the share of soups that repeated, their mean repeat_turn, soups per second).
+
 One JSON line on stdout; --out also writes it to a file.  There is no CPU fallback: without a GPU
 the script fails.
 """
@@ -167,6 +177,65 @@ def search_leg(a, res):
         print(json.dumps(row), file=sys.stderr, flush=True)
 
 
+PLANE_CASES = [(64, 64, "B3/S23", 16384), (512, 512, "B3/S23", 4096), (64, 64, "B38/S0236", 16384),
+               (512, 512, "B38/S0236", 4096)]
+
+
+def plane_leg(a, res):
+    """Torus and plane on the same soups, rule and max_turns, side by side in this process: the step
+    route over 4096 boards and the search over --soups soups."""
+    res["bench"] = "batch_plane"
+    res["soups"] = a.soups
+    del res["turns"]
+    assert a.soups >= 1 and a.soups % SEARCH_BATCH == 0, "--soups: a multiple of 4096"
+    box = tuple(int(v) for v in a.box.split("x")) if a.box else None
+    res["soup_box"] = box
+    seeds = np.arange(a.soups, dtype=np.uint64)
+    rules = [golhip.rule_string(*golhip.parse_rule(r)) for r in a.rule.split(",")] if a.rule else None
+    for w, h, rule, max_turns in PLANE_CASES:
+        if a.shapes and (w, h) not in [tuple(int(v) for v in t.split("x")) for t in a.shapes.split(",")]:
+            continue
+        if rules and golhip.rule_string(*golhip.parse_rule(rule)) not in rules:
+            continue
+        max_turns = a.max_turns or max_turns
+        row = {"width": w, "height": h, "rule": rule, "max_turns": max_turns}
+        for topology in ("torus", "plane"):
+            with golhip.Batch(w, h, SEARCH_BATCH, rule=rule, topology=topology, soup_box=box) as b:
+
+                def step_route():
+                    b.init_random(seeds=seeds[:SEARCH_BATCH])
+                    b.track_period()
+                    b.step(max_turns)
+                    return b.periods()
+
+                def search():
+                    return b.search(a.soups, seeds=seeds, max_turns=max_turns)
+
+                turns, periods = step_route()
+                got = search()
+                head = got[:SEARCH_BATCH]
+                assert np.array_equal(head["repeat_turn"], turns) and np.array_equal(head["period"], periods), \
+                    (w, h, rule, topology)
+                step_med, step_min = median_s(step_route, 2, a.calls)
+                search_med, search_min = median_s(search, 2, a.calls)
+                rt = got["repeat_turn"]
+                row[topology] = {
+                    "kernel_form": b.kernel_form,
+                    "step_route_ms_median": round(step_med * 1e3, 3), "step_route_ms_min": round(step_min * 1e3, 3),
+                    "step_route_gcups": round(SEARCH_BATCH * w * h * max_turns / step_med / 1e9, 1),
+                    "search_ms_median": round(search_med * 1e3, 3), "search_ms_min": round(search_min * 1e3, 3),
+                    "search_soups_per_s": round(a.soups / search_med, 1),
+                    "share_repeated": round(float((rt > 0).mean()), 4),
+                    "mean_repeat_turn": round(float(rt[rt > 0].mean()), 1) if (rt > 0).any() else None,
+                    "max_period": int(got["period"].max()),
+                    "mean_stop_turn": round(float(got["stop_turn"].mean()), 1)}
+        row["plane_over_torus_step_route"] = round(row["plane"]["step_route_ms_median"] /
+                                                   row["torus"]["step_route_ms_median"], 3)
+        row["plane_over_torus_search"] = round(row["plane"]["search_ms_median"] / row["torus"]["search_ms_median"], 3)
+        res["shapes"].append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=7)
@@ -179,10 +248,24 @@ def main():
     ap.add_argument("--batches", help="e.g. 256,4096 (default: 1,256,4096,65536)")
     ap.add_argument("--period", action="store_true", help="the cost of period tracking (see above)")
     ap.add_argument("--search", action="store_true", help="the soup search against the step route (see above)")
-    ap.add_argument("--soups", type=int, default=4096, help="--search: soups per call, a multiple of 4096")
+    ap.add_argument("--soups", type=int, default=4096, help="--search, --plane: soups per call, a multiple of 4096")
+    ap.add_argument("--plane", action="store_true", help="the plane beside the torus (see above)")
+    ap.add_argument("--box", help="--plane: the soup box, e.g. 16x16")
+    ap.add_argument("--max-turns", type=int, help="--plane: instead of the cases' max_turns")
     a = ap.parse_args()
     assert a.calls >= 7
     assert a.rule or not a.per_board_rules, "--per-board-rules needs --rule"
+    if a.plane:  # --rule here selects among the leg's cases ("B3/S23,B38/S0236")
+        assert not (a.search or a.period or a.per_board_rules), "--plane replaces the other legs"
+        res = {"bench": "batch_plane", "version": golhip.load_library().golhip_version(), "turns": None,
+               "calls": a.calls, "shapes": []}
+        plane_leg(a, res)
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            a.out.parent.mkdir(parents=True, exist_ok=True)
+            a.out.write_text(line + "\n")
+        return
     shapes = [tuple(int(v) for v in t.split("x")) for t in a.shapes.split(",")] if a.shapes else SHAPES
     batches = [int(v) for v in a.batches.split(",")] if a.batches else BATCHES
     rule = golhip.parse_rule(a.rule) if a.rule else None
