@@ -25,12 +25,16 @@
 // boards of the batch.  The handle lends its size, device, stream and uniform rule; its boards, turn,
 // records and switches are not touched.  Soups go out in chunks of at most kSearchChunk soups and
 // at most 2^44 cell updates, so that no launch runs long on a shared device.
+// golhip_batch_search_exact is the same call with a second pass per chunk, gol_batch_cycle
+// (batch_cycle.hpp), which turns each record's (repeat_turn, period) into the soup's cycle_start, the
+// first turn of its cycle; launch_batch_cycle below picks its functor.
 //
 // Device memory is allocated at create (the boards, the per-board counters, the transfer stage), by
 // the first golhip_batch_track_settle(b, 1) (board(t - 1) of every board), by the first
 // golhip_batch_track_period(b, 1) (every board's snapshot and its repeat turn) and by the first
-// golhip_batch_set_rules (the per-board rule pairs) and by the first golhip_batch_search (one chunk's
-// seeds, rule pairs and records); no other call allocates.  Bytes in and out,
+// golhip_batch_set_rules (the per-board rule pairs) and by the first golhip_batch_search or
+// golhip_batch_search_exact (one chunk's seeds, rule pairs, records and cycle starts); no other call
+// allocates.  Bytes in and out,
 // the seeds of init_random, per-board rules and counts and the per-turn history all pass through
 // the stage in chunks.
 #include <algorithm>
@@ -65,10 +69,11 @@ struct golhip_batch {
     bool per_board = false;              // the boards run `rules`, not `rule`
     uint32_t *rules = nullptr;           // device: nboards (birth, survive) pairs
     std::vector<uint32_t> rules_host;    // the same pairs, for golhip_batch_get_rules
-    // golhip_batch_search: one chunk's seeds, rule pairs and records
+    // golhip_batch_search / _search_exact: one chunk's seeds, rule pairs and records
     uint64_t *search_seeds = nullptr;
     uint32_t *search_rules = nullptr;
     golhip::SoupRecord *search_out = nullptr;
+    int64_t *search_cycle = nullptr;  // golhip_batch_search_exact: the chunk's cycle starts
     int topology = GOLHIP_TOPOLOGY_TORUS;
     int box_w = 0, box_h = 0;  // the soup box of init_random and search; 0, 0: the whole board
     std::string err;
@@ -114,6 +119,7 @@ void batch_free(golhip_batch_t b) {
     if (b->search_seeds) (void)hipFree(b->search_seeds);
     if (b->search_rules) (void)hipFree(b->search_rules);
     if (b->search_out) (void)hipFree(b->search_out);
+    if (b->search_cycle) (void)hipFree(b->search_cycle);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     b->boards = b->prev = b->rules = b->snap = nullptr;
     b->last_diff = nullptr;
@@ -122,6 +128,7 @@ void batch_free(golhip_batch_t b) {
     b->search_seeds = nullptr;
     b->search_rules = nullptr;
     b->search_out = nullptr;
+    b->search_cycle = nullptr;
     b->stream = nullptr;
 }
 
@@ -226,6 +233,25 @@ int rule_change_allowed(golhip_batch_t b) {
 }
 
 }  // namespace
+
+// The exact pass behind a chunk's search launch: gol_batch_cycle under B3/S23's rule step for a uniform
+// B3/S23, in the table form for every other rule and for per-soup rules (a catalogue rule too: the
+// pass has no constant-folded kernels).  A missing kernel is an error.
+hipError_t launch_batch_cycle(int W, int R, int nsoups, const BatchCycleParams &cp, hipStream_t s) {
+    const BatchSearchParams &sp = cp.bp.s;
+    const SoupBox &bx = cp.bp.box;
+    if (sp.max_turns < 1 || sp.max_turns > kSearchMaxTurns || nsoups < 1 || !sp.out || !cp.cycle_start ||
+        (sp.wd != 4 && sp.wd != 8 && sp.wd != 16) || sp.width < 64 || sp.width % 64 != 0 || sp.width > 32 * sp.wd ||
+        (sp.width & (sp.width - 1)) != 0)
+        return hipErrorInvalidValue;
+    if (bx.w < 1 || bx.h < 1 || bx.x0 < 0 || bx.y0 < 0 || bx.x0 + bx.w > sp.width || bx.y0 + bx.h > 4 * W * R)
+        return hipErrorInvalidValue;
+    if (!sp.rules && ((sp.rule.birth | sp.rule.survive) & ~kRuleMaskBits)) return hipErrorInvalidValue;
+    if (!sp.rules && sp.rule.birth == kLifeBirth && sp.rule.survive == kLifeSurvive)
+        return launch_batch_cycle_life(W, R, nsoups, cp, s);
+    return launch_batch_cycle_table(W, R, nsoups, cp, s);
+}
+
 }  // namespace golhip
 
 using namespace golhip;
@@ -552,8 +578,12 @@ int golhip_batch_get_rules(golhip_batch_t b, uint32_t *birth, uint32_t *survive)
     return GOLHIP_OK;
 }
 
-int golhip_batch_search(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds, uint64_t seed0, uint32_t density_q32,
-                        int64_t max_turns, const uint32_t *birth, const uint32_t *survive, golhip_soup_t *out) {
+// golhip_batch_search (exact == false: cycle_start is not looked at) and golhip_batch_search_exact: the
+// same checks, chunks and search launches; the exact call adds gol_batch_cycle behind each chunk's
+// search launch and one more copy.
+static int search_run(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds, uint64_t seed0, uint32_t density_q32,
+                      int64_t max_turns, const uint32_t *birth, const uint32_t *survive, golhip_soup_t *out,
+                      int64_t *cycle_start, bool exact) {
     if (!b) return GOLHIP_ERR_ARG;
     if (b->width % 64 != 0)
         return bfail(b, GOLHIP_ERR_ARG, "search needs width %% 64 == 0, as init_random (width %lld)", (long long)b->width);
@@ -571,6 +601,7 @@ int golhip_batch_search(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds,
     }
     if (nsoups == 0) return GOLHIP_OK;
     if (!out) return bfail(b, GOLHIP_ERR_ARG, "out is null");
+    if (exact && !cycle_start) return bfail(b, GOLHIP_ERR_ARG, "cycle_start is null");
     static_assert(sizeof(golhip_soup_t) == 32 && sizeof(SoupRecord) == 32, "a soup's record is 32 bytes");
     static_assert(offsetof(golhip_soup_t, repeat_turn) == offsetof(SoupRecord, repeat_turn) &&
                       offsetof(golhip_soup_t, period) == offsetof(SoupRecord, period) &&
@@ -582,6 +613,7 @@ int golhip_batch_search(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds,
     if (!b->search_seeds) BHIPCHK(b, hipMalloc(&b->search_seeds, sizeof(uint64_t) * (size_t)kSearchChunk));
     if (!b->search_rules) BHIPCHK(b, hipMalloc(&b->search_rules, 2 * sizeof(uint32_t) * (size_t)kSearchChunk));
     if (!b->search_out) BHIPCHK(b, hipMalloc(&b->search_out, sizeof(SoupRecord) * (size_t)kSearchChunk));
+    if (!b->search_cycle) BHIPCHK(b, hipMalloc(&b->search_cycle, sizeof(int64_t) * (size_t)kSearchChunk));
     // a chunk: at most kSearchChunk soups and at most 2^44 cell updates if no soup repeats, at least 1
     const int64_t chunk = std::max<int64_t>(
         1, std::min<int64_t>(kSearchChunk, kSearchChunkUpdates / (b->width * b->height * max_turns)));
@@ -621,9 +653,26 @@ int golhip_batch_search(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds,
         }
         BHIPCHK(b, hipMemcpyAsync(out + i, b->search_out, sizeof(SoupRecord) * (size_t)n, hipMemcpyDeviceToHost,
                                   b->stream));
+        if (exact) {  // the second pass reads the chunk's records on the device (stream order)
+            const BatchCycleParams cp{{sp, soup_box(b), b->topology == GOLHIP_TOPOLOGY_PLANE ? 1 : 0}, b->search_cycle};
+            BHIPCHK(b, launch_batch_cycle(b->W, b->R, (int)n, cp, b->stream));
+            BHIPCHK(b, hipMemcpyAsync(cycle_start + i, b->search_cycle, sizeof(int64_t) * (size_t)n,
+                                      hipMemcpyDeviceToHost, b->stream));
+        }
         BHIPCHK(b, hipStreamSynchronize(b->stream));  // the next chunk rewrites the buffers (and `pairs`)
     }
     return GOLHIP_OK;
+}
+
+int golhip_batch_search(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds, uint64_t seed0, uint32_t density_q32,
+                        int64_t max_turns, const uint32_t *birth, const uint32_t *survive, golhip_soup_t *out) {
+    return search_run(b, nsoups, seeds, seed0, density_q32, max_turns, birth, survive, out, nullptr, false);
+}
+
+int golhip_batch_search_exact(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds, uint64_t seed0,
+                              uint32_t density_q32, int64_t max_turns, const uint32_t *birth, const uint32_t *survive,
+                              golhip_soup_t *out, int64_t *cycle_start) {
+    return search_run(b, nsoups, seeds, seed0, density_q32, max_turns, birth, survive, out, cycle_start, true);
 }
 
 int golhip_batch_set_topology(golhip_batch_t b, int topology) {

@@ -427,6 +427,20 @@ struct BatchBoxSearchParams {
 };
 hipError_t launch_plane_search(int W, int R, int nsoups, const BatchBoxSearchParams &bp, hipStream_t s);
 hipError_t launch_plane_search_life(int W, int R, int nsoups, const BatchBoxSearchParams &bp, hipStream_t s);
+// The exact pass of golhip_batch_search_exact (gol_batch_cycle, batch_cycle.hpp; translation units
+// batch_cycle_life.hip and batch_cycle_table.hip).  It runs after launch_batch_search or
+// launch_plane_search on the same chunk with the same parameters (bp.box the whole board and
+// bp.plane 0 for an unboxed torus), reads soup i's (repeat_turn, period) from bp.s.out[i] and writes
+// cycle_start[i]: the least t >= 0 with board(t + period) == board(t), -1 without a repeat.  Two
+// functors: B3/S23's rule step for a uniform B3/S23, the table form for everything else;
+// launch_batch_cycle (engine_batch.hip) checks the parameters and picks one.
+struct BatchCycleParams {
+    BatchBoxSearchParams bp;
+    int64_t *cycle_start;  // device memory, one per soup of the launch
+};
+hipError_t launch_batch_cycle(int W, int R, int nsoups, const BatchCycleParams &cp, hipStream_t s);
+hipError_t launch_batch_cycle_life(int W, int R, int nsoups, const BatchCycleParams &cp, hipStream_t s);
+hipError_t launch_batch_cycle_table(int W, int R, int nsoups, const BatchCycleParams &cp, hipStream_t s);
 // Clears every cell outside the box in boards of the batch layout (after launch_batch_init_random).
 hipError_t launch_batch_clip_box(uint32_t *boards, int64_t board_pitch, int64_t nboards, int64_t rows, int64_t width,
                                  int32_t wd, const SoupBox &box, hipStream_t s);

@@ -65,6 +65,7 @@ EXPORTS = [
     "golhip_batch_set_rule", "golhip_batch_set_rule_masks", "golhip_batch_get_rule", "golhip_batch_set_rules",
     "golhip_batch_get_rules", "golhip_batch_kernel",
     "golhip_batch_track_period", "golhip_batch_periods", "golhip_batch_search",
+    "golhip_batch_search_exact",
     "golhip_batch_set_topology", "golhip_batch_get_topology", "golhip_batch_set_soup_box", "golhip_batch_get_soup_box",
 ]
 
@@ -90,6 +91,20 @@ def search_stop_turn(repeat_turn: int, max_turns: int) -> int:
     """The generations Batch.search runs a soup whose first repeat is at turn repeat_turn (-1: none
     within max_turns): max_turns, or min(max_turns, 32 * ((repeat_turn - 1) // 32) + 40)."""
     return max_turns if repeat_turn < 0 else min(max_turns, 32 * ((repeat_turn - 1) // 32) + 40)
+
+
+def cycle_start_floor(repeat_turn: int, period: int) -> int:
+    """The lower bound on cycle_start that a soup's record alone gives, the turn from which
+    Batch.search_exact compares: with s = repeat_turn - period = 2 ** j - 1 the snapshot turn,
+    2 ** (j - 1) - 1 if j > 0 and period <= 2 ** (j - 1) (the previous snapshot would have matched
+    within its window had the soup been on its cycle by then, so cycle_start is above it), else 0.
+    Always 0 <= floor <= cycle_start <= repeat_turn - period; 0 for a record without a repeat.  The
+    exact pass costs about floor + period + 2 * (cycle_start - floor) generations."""
+    s = int(repeat_turn) - int(period)
+    if repeat_turn < 0 or s <= 0:
+        return 0
+    half = (s + 1) // 2
+    return half - 1 if period <= half else 0
 
 
 class Xfer(ctypes.Structure):
@@ -271,6 +286,8 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
         "golhip_batch_periods": ([H, ctypes.c_void_p, ctypes.c_void_p], i32),
         "golhip_batch_search": ([H, i64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, i64, ctypes.c_void_p,
                                  ctypes.c_void_p, ctypes.c_void_p], i32),
+        "golhip_batch_search_exact": ([H, i64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, i64,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], i32),
         "golhip_batch_turn": ([H, i64p], i32),
         "golhip_batch_set_rule": ([H, ctypes.c_char_p], i32),
         "golhip_batch_set_rule_masks": ([H, ctypes.c_uint32, ctypes.c_uint32], i32),
@@ -843,7 +860,10 @@ class Batch:
 
     topology: "torus" (the default) or "plane", a bounded grid whose outside is dead (set_topology,
     topology).  soup_box: (w, h), the centred box outside which init_random and search clear every
-    cell of a soup, or None for the whole board (set_soup_box, soup_box)."""
+    cell of a soup, or None for the whole board (set_soup_box, soup_box).
+
+    Soups: search() runs seeds, not boards of the batch, each until it repeats; search_exact() adds
+    every soup's cycle_start, the exact turn at which it enters its cycle."""
 
     def __init__(self, width: int, height: int, nboards: int, device: int = 0, *,
                  rule: str | tuple[int, int] | None = None, rules=None, topology: str | int = "torus",
@@ -1036,6 +1056,36 @@ class Batch:
         self._check(self._L.golhip_batch_search(self._h, nsoups, sptr, seed0, density_q32, max_turns, bptr, vptr,
                                                 out.ctypes.data))
         return out
+
+    def search_exact(self, nsoups: int, *, seeds=None, seed0: int = 0, density_q32: int = DENSITY_HALF,
+                     max_turns: int, rules=None) -> tuple[np.ndarray, np.ndarray]:
+        """search() plus the exact turn at which each soup enters its cycle
+        (golhip_batch_search_exact).  Returns (records, cycle_start): records is byte for byte what
+        search() returns for the same arguments, cycle_start an int64 array with, for a soup that
+        repeated within max_turns, the least t >= 0 with board(t + period) == board(t) -- the soup's
+        lifespan, where repeat_turn is only the turn at which Brent's snapshots noticed the cycle,
+        always 2 ** j - 1 + period -- and -1 for a soup without a repeat.  0 <= cycle_start <=
+        repeat_turn - period, and 0 exactly when the soup itself is on its cycle.  The arguments, the
+        rule, the topology, the soup_box and the errors are search()'s; cycle_start depends on what
+        a record depends on and nothing else.  A second pass on the device (gol_batch_cycle) re-runs
+        each soup from its seed: about cycle_start_floor(repeat_turn, period) + period +
+        2 * (cycle_start - floor) generations on top of the search's."""
+        nsoups = int(nsoups)
+        sptr = bptr = vptr = None
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+            if seeds.shape != (max(nsoups, 0),):
+                raise GolHipError(ERR_ARG, f"seeds: shape {seeds.shape} for {nsoups} soups")
+            sptr = seeds.ctypes.data
+        if rules is not None:
+            pairs = self._pairs_of(rules, nsoups)
+            birth, survive = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+            bptr, vptr = birth.ctypes.data, survive.ctypes.data
+        out = np.zeros(max(nsoups, 0), dtype=SOUP_DTYPE)
+        cycle_start = np.zeros(max(nsoups, 0), dtype=np.int64)
+        self._check(self._L.golhip_batch_search_exact(self._h, nsoups, sptr, seed0, density_q32, max_turns, bptr,
+                                                      vptr, out.ctypes.data, cycle_start.ctypes.data))
+        return out, cycle_start
 
     @property
     def turn(self) -> int:

@@ -416,9 +416,10 @@ int golhip_edge_wait(golhip_t h, double *total_ms, int64_t *blocks);
  *   - Board i of a load or store sits at cells + (i - first) * board_stride + y * row_stride; input
  *     0 / nonzero, output 0 / 255.  No call but create, the first golhip_batch_track_settle(b, 1), the
  *     first golhip_batch_track_period(b, 1) (a second boards-sized buffer, the snapshots, and one
- *     int64 per board), the first golhip_batch_set_rules and the first golhip_batch_search (one chunk's
- *     seeds, rule pairs and records: 3 MiB) allocates device memory: bytes, seeds, rules, counts and
- *     history go through a transfer stage in chunks.
+ *     int64 per board), the first golhip_batch_set_rules and the first golhip_batch_search or
+ *     golhip_batch_search_exact (one chunk's seeds, rule pairs, records and cycle starts: 3.5 MiB)
+ *     allocates device memory: bytes, seeds, rules, counts and history go through a transfer stage
+ *     in chunks.
  *   - A batch has ONE turn counter.  Any golhip_batch_load_bytes, even of part of the batch, and any
  *     golhip_batch_init_random set it to 0 and clear every settle and period record: a batch is filled, then run.
  *   - golhip_batch_init_random: board i is bit for bit what golhip_init_random(seed_i, density_q32)
@@ -536,6 +537,42 @@ int golhip_batch_search(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds 
                         uint64_t seed0, uint32_t density_q32, int64_t max_turns,
                         const uint32_t *birth /* nsoups, or NULL */, const uint32_t *survive,
                         golhip_soup_t *out /* nsoups */);
+/* The exact search: golhip_batch_search plus, per soup, the turn at which it enters its cycle.
+ * repeat_turn is the turn at which Brent's scheme NOTICES the repeat, always 2^j - 1 + period: every
+ * soup whose ash forms between turn 1024 and turn 2047 reports 2048 (a still life), 2049 (blinkers)
+ * and so on.  The quantity a soup search ranks on is the lifespan, the first turn of the cycle:
+ *   - cycle_start[i], for a soup with a repeat within max_turns, is the least t >= 0 with
+ *     board_i(t + period) == board_i(t), period being the record's (the cycle's minimal period);
+ *     -1 for a soup without a repeat.
+ *   - 0 <= cycle_start <= repeat_turn - period.
+ *   - cycle_start + period <= repeat_turn <= max_turns: the exact pass never needs a generation
+ *     beyond repeat_turn.
+ *   - cycle_start == 0 exactly when board_i(0) is on the cycle (an empty board, a still life).
+ *   - On a plane, in a soup box and under per-soup rules the definition holds word for word with the
+ *     board stepped that way, as for every other field of the record.
+ *   - out is byte for byte what golhip_batch_search writes for the same arguments; golhip_soup_t and
+ *     golhip_batch_search are what they were.
+ *   - Errors: golhip_batch_search's checks, texts and contract (the handle, out and cycle_start are
+ *     then untouched); additionally cycle_start == NULL with nsoups > 0 is GOLHIP_ERR_ARG.
+ *   - Chunks: golhip_batch_search's; cycle_start does not depend on the chunking, on nsoups or on the
+ *     soup's position.  The chunk's device buffers hold 8 more bytes per soup (one chunk's seeds, rule
+ *     pairs, records and cycle starts: 3.5 MiB), allocated with the search buffers by the first
+ *     golhip_batch_search or golhip_batch_search_exact, whichever comes first, and freed by
+ *     golhip_batch_destroy.
+ *   - How: a second pass (gol_batch_cycle) behind each chunk's search launch, one workgroup per soup.
+ *     With s = repeat_turn - period = 2^j - 1 the record gives cycle_start <= s and, if j > 0 and
+ *     period <= 2^(j-1), cycle_start > 2^(j-1) - 1 (the previous snapshot would have matched inside
+ *     its window otherwise); lo is that bound, else 0.  The pass re-seeds the soup, runs it lo
+ *     generations, keeps a copy, runs it `period` more and then steps both in lockstep, comparing
+ *     board(t + period) with board(t) from t = lo until they are equal: lo + period +
+ *     2 (cycle_start - lo) generations plus at most 34 lockstep turns of detection slack, never
+ *     above about 1.5 s + period.  Two forms: B3/S23's rule step for a uniform B3/S23, the table form
+ *     for every other rule: a HighLife search runs its exact pass in the table form, and the
+ *     results are the rule's, not the form's. */
+int golhip_batch_search_exact(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds /* nsoups, or NULL */,
+                              uint64_t seed0, uint32_t density_q32, int64_t max_turns,
+                              const uint32_t *birth /* nsoups, or NULL */, const uint32_t *survive,
+                              golhip_soup_t *out /* nsoups */, int64_t *cycle_start /* nsoups */);
 /* Topology and the soup box: the standard search setting, a small random box in empty space on a
  * bounded grid whose outside is dead (Golly's :P64,64 where the torus is :T64,64).
  *   - A batch starts as a torus.  On GOLHIP_TOPOLOGY_PLANE the board is the same width x height

@@ -51,6 +51,16 @@ routes.  The cases: 64 x 64 and 512 x 512 under B3/S23 and under B38/S0236 (the 
 --max-turns overrides their max_turns.  --box WxH adds the soup box to every batch of this leg
 (the boxed search: the share of soups that repeated, their mean repeat_turn, soups per second).
 
+--exact: the exact search (Batch.search_exact: the search plus gol_batch_cycle, which gives every
+soup's cycle_start) beside the plain search, instead of the run above: one search_exact call and
+one search call on the same --soups soups (seeds 0 .. --soups - 1, any count), 64 x 64 under B3/S23
+and under HighLife (whose exact pass runs the table form) at max_turns 16384.  Before anything is
+timed the records must agree byte for byte and cycle_start must lie between cycle_start_floor and
+repeat_turn - period.  Reported: both call times and their ratio, mean cycle_start beside mean
+repeat_turn, and the generations the pass adds (floor + period + 2 (cycle_start - floor), summed
+over the soups that repeated) over the sum of repeat_turn and over the sum of stop_turn, the
+generations the search itself ran: the ratio the time ratio should track.
+
 One JSON line on stdout; --out also writes it to a file.  There is no CPU fallback: without a GPU
 the script fails.
 """
@@ -236,6 +246,56 @@ def plane_leg(a, res):
         print(json.dumps(row), file=sys.stderr, flush=True)
 
 
+EXACT_CASES = [(64, 64, "B3/S23", 16384), (64, 64, "B36/S23", 16384)]
+
+
+def exact_leg(a, res):
+    """Batch.search_exact beside Batch.search on the same soups, rule and max_turns, in this process."""
+    res["bench"] = "batch_cycle"
+    res["soups"] = a.soups
+    del res["turns"]
+    assert a.soups >= 1
+    seeds = np.arange(a.soups, dtype=np.uint64)
+    for w, h, rule, max_turns in EXACT_CASES:
+        max_turns = a.max_turns or max_turns
+        with golhip.Batch(w, h, 1, rule=rule) as b:
+            form = b.kernel_form
+
+            def search():
+                return b.search(a.soups, seeds=seeds, max_turns=max_turns)
+
+            def exact():
+                return b.search_exact(a.soups, seeds=seeds, max_turns=max_turns)
+
+            rec = search()
+            got, start = exact()
+            assert got.tobytes() == rec.tobytes(), (w, h, rule)
+            rep, per = rec["repeat_turn"], rec["period"]
+            found = rep > 0
+            assert (start[~found] == -1).all() and (start[found] >= 0).all(), (w, h, rule)
+            assert (start[found] <= (rep - per)[found]).all(), (w, h, rule)
+            lo = np.array([golhip.cycle_start_floor(int(r), int(p)) for r, p in zip(rep, per)], dtype=np.int64)
+            assert (lo[found] <= start[found]).all(), (w, h, rule)
+            search_med, search_min = median_s(search, 2, a.calls)
+            exact_med, exact_min = median_s(exact, 2, a.calls)
+        extra = (lo + per + 2 * (start - lo))[found]  # the pass's generations, without its detection slack
+        row = {"width": w, "height": h, "rule": rule, "search_kernel_form": form, "max_turns": max_turns,
+               "soups_with_a_repeat": int(found.sum()),
+               "mean_repeat_turn": round(float(rep[found].mean()), 1) if found.any() else None,
+               "mean_cycle_start": round(float(start[found].mean()), 1) if found.any() else None,
+               "max_cycle_start": int(start.max()),
+               "mean_stop_turn": round(float(rec["stop_turn"].mean()), 1),
+               "cycle_start_below_snapshot_turn": int((start < rep - per)[found].sum()),
+               "generations_ratio_over_repeat_turn": round(float(extra.sum() / rep[found].sum()), 4) if found.any() else None,
+               "generations_ratio_over_stop_turn": round(float(extra.sum() / rec["stop_turn"].sum()), 4),
+               "search_ms_median": round(search_med * 1e3, 3), "search_ms_min": round(search_min * 1e3, 3),
+               "exact_ms_median": round(exact_med * 1e3, 3), "exact_ms_min": round(exact_min * 1e3, 3),
+               "search_soups_per_s": round(a.soups / search_med, 1), "exact_soups_per_s": round(a.soups / exact_med, 1),
+               "exact_over_search": round(exact_med / search_med, 3)}
+        res["shapes"].append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=7)
@@ -251,10 +311,22 @@ def main():
     ap.add_argument("--soups", type=int, default=4096, help="--search, --plane: soups per call, a multiple of 4096")
     ap.add_argument("--plane", action="store_true", help="the plane beside the torus (see above)")
     ap.add_argument("--box", help="--plane: the soup box, e.g. 16x16")
-    ap.add_argument("--max-turns", type=int, help="--plane: instead of the cases' max_turns")
+    ap.add_argument("--max-turns", type=int, help="--plane, --exact: instead of the cases' max_turns")
+    ap.add_argument("--exact", action="store_true", help="search_exact beside search (see above)")
     a = ap.parse_args()
     assert a.calls >= 7
     assert a.rule or not a.per_board_rules, "--per-board-rules needs --rule"
+    if a.exact:
+        assert not (a.plane or a.search or a.period or a.rule), "--exact has its own rules and replaces the other legs"
+        res = {"bench": "batch_cycle", "version": golhip.load_library().golhip_version(), "turns": None,
+               "calls": a.calls, "shapes": []}
+        exact_leg(a, res)
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            a.out.parent.mkdir(parents=True, exist_ok=True)
+            a.out.write_text(line + "\n")
+        return
     if a.plane:  # --rule here selects among the leg's cases ("B3/S23,B38/S0236")
         assert not (a.search or a.period or a.per_board_rules), "--plane replaces the other legs"
         res = {"bench": "batch_plane", "version": golhip.load_library().golhip_version(), "turns": None,
