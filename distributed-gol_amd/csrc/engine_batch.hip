@@ -33,10 +33,13 @@
 // the first golhip_batch_track_settle(b, 1) (board(t - 1) of every board), by the first
 // golhip_batch_track_period(b, 1) (every board's snapshot and its repeat turn) and by the first
 // golhip_batch_set_rules (the per-board rule pairs) and by the first golhip_batch_search or
-// golhip_batch_search_exact (one chunk's seeds, rule pairs, records and cycle starts); no other call
-// allocates.  Bytes in and out,
-// the seeds of init_random, per-board rules and counts and the per-turn history all pass through
-// the stage in chunks.
+// golhip_batch_search_exact (one chunk's seeds, rule pairs, records and cycle starts) and by the first
+// golhip_batch_census (the pattern table, 66 KiB); no other call allocates.  Bytes in and out,
+// the seeds of init_random, per-board rules and counts, the per-turn history and the census's counts
+// and residues all pass through the stage in chunks.
+//
+// The census (golhip_batch_census) runs gol_batch_census (batch_census.hpp) over the boards as they are:
+// it reads the boards and the topology and writes nothing the handle owns.
 #include <algorithm>
 #include <cstdarg>
 #include <cstddef>
@@ -74,6 +77,7 @@ struct golhip_batch {
     uint32_t *search_rules = nullptr;
     golhip::SoupRecord *search_out = nullptr;
     int64_t *search_cycle = nullptr;  // golhip_batch_search_exact: the chunk's cycle starts
+    golhip::CensusPattern *census_pat = nullptr;  // golhip_batch_census: the pattern table of a call
     int topology = GOLHIP_TOPOLOGY_TORUS;
     int box_w = 0, box_h = 0;  // the soup box of init_random and search; 0, 0: the whole board
     std::string err;
@@ -120,6 +124,7 @@ void batch_free(golhip_batch_t b) {
     if (b->search_rules) (void)hipFree(b->search_rules);
     if (b->search_out) (void)hipFree(b->search_out);
     if (b->search_cycle) (void)hipFree(b->search_cycle);
+    if (b->census_pat) (void)hipFree(b->census_pat);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     b->boards = b->prev = b->rules = b->snap = nullptr;
     b->last_diff = nullptr;
@@ -129,6 +134,7 @@ void batch_free(golhip_batch_t b) {
     b->search_rules = nullptr;
     b->search_out = nullptr;
     b->search_cycle = nullptr;
+    b->census_pat = nullptr;
     b->stream = nullptr;
 }
 
@@ -673,6 +679,106 @@ int golhip_batch_search_exact(golhip_batch_t b, int64_t nsoups, const uint64_t *
                               uint32_t density_q32, int64_t max_turns, const uint32_t *birth, const uint32_t *survive,
                               golhip_soup_t *out, int64_t *cycle_start) {
     return search_run(b, nsoups, seeds, seed0, density_q32, max_turns, birth, survive, out, cycle_start, true);
+}
+
+// The checks of golhip_batch_census's pattern list; the text names the pattern index and the offence.
+static int census_check(golhip_batch_t b, const golhip_pattern_t *patterns, int npat) {
+    for (int p = 0; p < npat; ++p) {
+        const golhip_pattern_t &q = patterns[p];
+        if (q.w < 1 || q.w > 32 || q.h < 1 || q.h > 32)
+            return bfail(b, GOLHIP_ERR_ARG, "pattern %d: w %d, h %d: 1..32 each", p, q.w, q.h);
+        if (q.w > b->width || q.h > b->height)
+            return bfail(b, GOLHIP_ERR_ARG, "pattern %d: %d x %d is larger than the %lld x %lld board", p, q.w, q.h,
+                         (long long)b->width, (long long)b->height);
+        const uint32_t cols = q.w == 32 ? ~0u : (1u << q.w) - 1u;
+        uint32_t live = 0;
+        for (int r = 0; r < 32; ++r) {
+            const uint32_t bits = q.alive[r] | q.care[r];
+            if (r >= q.h && bits)
+                return bfail(b, GOLHIP_ERR_ARG, "pattern %d: a bit in row %d, the pattern has %d rows", p, r, q.h);
+            if (bits & ~cols)
+                return bfail(b, GOLHIP_ERR_ARG, "pattern %d: row %d has a bit at a column >= w (%d)", p, r, q.w);
+            if (q.alive[r] & ~q.care[r])
+                return bfail(b, GOLHIP_ERR_ARG, "pattern %d: row %d: alive 0x%x is not a subset of care 0x%x", p, r,
+                             q.alive[r], q.care[r]);
+            live |= q.alive[r];
+        }
+        if (!live) return bfail(b, GOLHIP_ERR_ARG, "pattern %d: no live cell", p);
+    }
+    return GOLHIP_OK;
+}
+
+int golhip_batch_census(golhip_batch_t b, const golhip_pattern_t *patterns, int npat, uint32_t *counts,
+                        uint32_t *residue) {
+    if (!b) return GOLHIP_ERR_ARG;
+    static_assert(sizeof(golhip_pattern_t) == 264 && sizeof(CensusPattern) == 264 &&
+                      offsetof(golhip_pattern_t, alive) == offsetof(CensusPattern, alive) &&
+                      offsetof(golhip_pattern_t, care) == offsetof(CensusPattern, care),
+                  "the kernel's pattern is golhip_pattern_t");
+    if (npat < 0 || npat > kCensusMaxPatterns)
+        return bfail(b, GOLHIP_ERR_ARG, "census npat %d: 0 to %d patterns", npat, kCensusMaxPatterns);
+    if (npat > 0 && !patterns) return bfail(b, GOLHIP_ERR_ARG, "census patterns is null with npat %d", npat);
+    if (!counts && !residue) return bfail(b, GOLHIP_ERR_ARG, "census counts and residue are both null");
+    int rc = census_check(b, patterns, npat);
+    if (rc) return rc;
+    if (npat == 0)  // nothing matches, nothing is covered; counts has no columns
+        return residue ? golhip_batch_alive_counts(b, residue) : GOLHIP_OK;
+    BHIPCHK(b, hipSetDevice(b->device));
+    if (!b->census_pat) BHIPCHK(b, hipMalloc(&b->census_pat, sizeof(CensusPattern) * (size_t)kCensusMaxPatterns));
+    BHIPCHK(b, hipMemcpyAsync(b->census_pat, patterns, sizeof(CensusPattern) * (size_t)npat, hipMemcpyHostToDevice,
+                              b->stream));
+    BatchCensusParams cp{};
+    cp.board_pitch = b->board_words;
+    cp.wd = b->wd;
+    cp.width = (int32_t)b->width;
+    cp.height = (int32_t)b->height;
+    cp.plane = b->topology == GOLHIP_TOPOLOGY_PLANE ? 1 : 0;
+    uint32_t *stage = reinterpret_cast<uint32_t *>(b->stage);
+    const int64_t cap = b->stage_bytes / 4;  // >= nboards >= 1 words
+    // The results come back through the stage.  Where it holds a board's npat counts and its residue,
+    // one pass: chunks of boards, each launch writing both.  A smaller stage (GOLHIP_STAGE_BYTES) takes the
+    // counts in groups of patterns -- counts[.., p] does not depend on the other patterns -- and the
+    // residue in a pass of its own over the whole list.
+    const int64_t per_board = (counts ? npat : 0) + (residue ? 1 : 0);
+    const bool one_pass = per_board <= cap;
+    const int64_t pgroup = one_pass ? npat : std::min<int64_t>(npat, cap);
+    for (int64_t p0 = 0; counts && p0 < npat; p0 += pgroup) {
+        const int64_t np = std::min<int64_t>(pgroup, npat - p0);
+        const bool both = one_pass && residue;
+        const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(kSearchChunk, cap / (np + (both ? 1 : 0))));
+        for (int64_t i = 0; i < b->nboards; i += chunk) {
+            const int64_t n = std::min<int64_t>(chunk, b->nboards - i);
+            cp.boards = b->boards + i * b->board_words;
+            cp.patterns = b->census_pat + p0;
+            cp.npat = (int32_t)np;
+            cp.counts = stage;
+            cp.residue = both ? stage + n * np : nullptr;
+            BHIPCHK(b, launch_batch_census((int)n, cp, b->stream));  // a missing kernel is an error
+            BHIPCHK(b, hipMemcpy2DAsync(counts + i * npat + p0, sizeof(uint32_t) * (size_t)npat, stage,
+                                        sizeof(uint32_t) * (size_t)np, sizeof(uint32_t) * (size_t)np, (size_t)n,
+                                        hipMemcpyDeviceToHost, b->stream));
+            if (both)
+                BHIPCHK(b, hipMemcpyAsync(residue + i, cp.residue, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost,
+                                          b->stream));
+            BHIPCHK(b, hipStreamSynchronize(b->stream));  // the next launch rewrites the stage
+        }
+    }
+    if (residue && !(counts && one_pass)) {
+        const int64_t chunk = std::min<int64_t>(kSearchChunk, cap);
+        for (int64_t i = 0; i < b->nboards; i += chunk) {
+            const int64_t n = std::min<int64_t>(chunk, b->nboards - i);
+            cp.boards = b->boards + i * b->board_words;
+            cp.patterns = b->census_pat;
+            cp.npat = npat;
+            cp.counts = nullptr;
+            cp.residue = stage;
+            BHIPCHK(b, launch_batch_census((int)n, cp, b->stream));
+            BHIPCHK(b, hipMemcpyAsync(residue + i, stage, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, b->stream));
+            BHIPCHK(b, hipStreamSynchronize(b->stream));
+        }
+    }
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    return GOLHIP_OK;
 }
 
 int golhip_batch_set_topology(golhip_batch_t b, int topology) {

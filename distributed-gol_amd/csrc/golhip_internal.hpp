@@ -441,6 +441,27 @@ struct BatchCycleParams {
 hipError_t launch_batch_cycle(int W, int R, int nsoups, const BatchCycleParams &cp, hipStream_t s);
 hipError_t launch_batch_cycle_life(int W, int R, int nsoups, const BatchCycleParams &cp, hipStream_t s);
 hipError_t launch_batch_cycle_table(int W, int R, int nsoups, const BatchCycleParams &cp, hipStream_t s);
+// The census (gol_batch_census, batch_census.hpp; ONE kernel in one translation unit, batch_census.hip,
+// with run-time width, height, topology and pattern table): board i of the launch is boards + i *
+// board_pitch in the batch layout, nboards <= 65536.  counts[i * npat + p] = the anchors at which
+// pattern p matches board i, residue[i] = the live cells of board i that no match covers
+// (include/golhip.h: golhip_batch_census); either may be null, not both.  A null residue skips the
+// cover work.  All pointers are device memory.
+struct CensusPattern {  // golhip_pattern_t (include/golhip.h)
+    int32_t w, h;
+    uint32_t alive[32], care[32];
+};
+constexpr int kCensusMaxPatterns = 256;
+struct BatchCensusParams {
+    const uint32_t *boards;
+    int64_t board_pitch;
+    int32_t wd, width, height;  // words per torus row, cells per board row, rows
+    int32_t plane;
+    const CensusPattern *patterns;
+    int32_t npat;  // 1 .. kCensusMaxPatterns
+    uint32_t *counts, *residue;
+};
+hipError_t launch_batch_census(int nboards, const BatchCensusParams &cp, hipStream_t s);
 // Clears every cell outside the box in boards of the batch layout (after launch_batch_init_random).
 hipError_t launch_batch_clip_box(uint32_t *boards, int64_t board_pitch, int64_t nboards, int64_t rows, int64_t width,
                                  int32_t wd, const SoupBox &box, hipStream_t s);

@@ -67,6 +67,7 @@ EXPORTS = [
     "golhip_batch_track_period", "golhip_batch_periods", "golhip_batch_search",
     "golhip_batch_search_exact",
     "golhip_batch_set_topology", "golhip_batch_get_topology", "golhip_batch_set_soup_box", "golhip_batch_get_soup_box",
+    "golhip_batch_census",
 ]
 
 
@@ -105,6 +106,86 @@ def cycle_start_floor(repeat_turn: int, period: int) -> int:
         return 0
     half = (s + 1) // 2
     return half - 1 if period <= half else 0
+
+
+class Pattern(ctypes.Structure):
+    """golhip_pattern_t: one pattern of Batch.census, h rows of w cells (1..32 each).  Bit c of alive[r]:
+    cell (r, c) must be alive; bit c of care[r]: cell (r, c) is looked at (alive is a subset of care)."""
+    _fields_ = [("w", ctypes.c_int32), ("h", ctypes.c_int32), ("alive", ctypes.c_uint32 * 32),
+                ("care", ctypes.c_uint32 * 32)]
+
+
+CENSUS_MAX_PATTERNS = 256
+
+
+def pattern(cells) -> Pattern:
+    """The Pattern of a 2-D array: 1 = the cell must be alive, 0 = it must be dead, -1 = it is not
+    looked at.  GolHipError(ERR_ARG), without touching a device, for what golhip_batch_census refuses
+    in a pattern: not 2-D, a side outside 1..32, a value other than 1, 0 or -1, no live cell."""
+    a = np.asarray(cells)
+    if a.ndim != 2:
+        raise GolHipError(ERR_ARG, f"pattern: a 2-D array of 1, 0 and -1, not {a.ndim}-D")
+    h, w = a.shape
+    if not (1 <= w <= 32 and 1 <= h <= 32):
+        raise GolHipError(ERR_ARG, f"pattern: w {w}, h {h}: 1..32 each")
+    if not np.isin(a, (-1, 0, 1)).all():
+        raise GolHipError(ERR_ARG, "pattern: cells are 1 (alive), 0 (dead) or -1 (not looked at)")
+    if not (a == 1).any():
+        raise GolHipError(ERR_ARG, "pattern: no live cell")
+    p = Pattern(w=w, h=h)
+    for r in range(h):
+        p.alive[r] = sum(1 << c for c in range(w) if a[r, c] == 1)
+        p.care[r] = sum(1 << c for c in range(w) if a[r, c] != -1)
+    return p
+
+
+def isolated(cells) -> np.ndarray:
+    """`cells` inside a ring of dead cells, one cell wide: as a pattern it matches the object only
+    where nothing touches it."""
+    return np.pad(np.asarray(cells, dtype=np.int8), 1)
+
+
+def orientations(cells) -> list[np.ndarray]:
+    """The distinct ones of the 8 rotations and reflections of `cells`, in a fixed order: the array
+    rotated by 0, 90, 180 and 270 degrees (numpy.rot90), then its left-right mirror image rotated
+    the same four ways; an array equal to an earlier one is left out."""
+    a = np.asarray(cells, dtype=np.int8)
+    out: list[np.ndarray] = []
+    for base in (a, np.fliplr(a)):
+        for k in range(4):
+            o = np.ascontiguousarray(np.rot90(base, k))
+            if not any(o.shape == q.shape and np.array_equal(o, q) for q in out):
+                out.append(o)
+    return out
+
+
+# the catalogue of common_objects(): every phase of each object, one orientation each
+_COMMON_OBJECTS = {
+    "block": ["OO/OO"],
+    "beehive": [".OO./O..O/.OO."],
+    "loaf": [".OO./O..O/.O.O/..O."],
+    "boat": ["OO./O.O/.O."],
+    "tub": [".O./O.O/.O."],
+    "pond": [".OO./O..O/O..O/.OO."],
+    "ship": ["OO./O.O/.OO"],
+    "blinker": ["OOO"],  # its other phase is its other orientation
+    "glider": [".O./..O/OOO", "O.O/.OO/.O."],  # the other two phases are mirror images of these
+}
+
+
+def common_objects() -> dict[str, list[np.ndarray]]:
+    """The commonest ash of B3/S23 as census patterns: name -> list of int8 arrays, each the object
+    inside its ring of dead cells (isolated), in every orientation and every phase.  block 1,
+    beehive 2, loaf 4, boat 4, tub 1, pond 1, ship 2, blinker 2 (its two phases), glider 16 (2 phases x
+    8 orientations, which hold all 4 phases): 33 arrays."""
+    out = {}
+    for name, phases in _COMMON_OBJECTS.items():
+        arrays: list[np.ndarray] = []
+        for text in phases:
+            cells = np.array([[ch == "O" for ch in row] for row in text.split("/")], dtype=np.int8)
+            arrays += [isolated(o) for o in orientations(cells)]
+        out[name] = arrays
+    return out
 
 
 class Xfer(ctypes.Structure):
@@ -299,6 +380,7 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
         "golhip_batch_get_topology": ([H, ctypes.POINTER(i32)], i32),
         "golhip_batch_set_soup_box": ([H, i32, i32], i32),
         "golhip_batch_get_soup_box": ([H, ctypes.POINTER(i32), ctypes.POINTER(i32)], i32),
+        "golhip_batch_census": ([H, ctypes.c_void_p, i32, ctypes.c_void_p, ctypes.c_void_p], i32),
         "golhip_launch_kind_counts": ([H, i32, i32, ctypes.POINTER(ctypes.c_int),
                                        ctypes.POINTER(ctypes.c_int)], i32),
     }
@@ -863,7 +945,9 @@ class Batch:
     cell of a soup, or None for the whole board (set_soup_box, soup_box).
 
     Soups: search() runs seeds, not boards of the batch, each until it repeats; search_exact() adds
-    every soup's cycle_start, the exact turn at which it enters its cycle."""
+    every soup's cycle_start, the exact turn at which it enters its cycle.  census() says what the
+    boards hold: per board, how often each pattern of a list matches and how many live cells no match
+    explains."""
 
     def __init__(self, width: int, height: int, nboards: int, device: int = 0, *,
                  rule: str | tuple[int, int] | None = None, rules=None, topology: str | int = "torus",
@@ -1086,6 +1170,50 @@ class Batch:
         self._check(self._L.golhip_batch_search_exact(self._h, nsoups, sptr, seed0, density_q32, max_turns, bptr,
                                                       vptr, out.ctypes.data, cycle_start.ctypes.data))
         return out, cycle_start
+
+    def census(self, patterns, *, counts: bool = True, residue: bool = True):
+        """What the boards hold, by pattern matching on the device (golhip_batch_census).  patterns is
+        a sequence of 2-D arrays (1 alive, 0 dead, -1 not looked at: pattern()) or Patterns, at most
+        256, e.g. the arrays of common_objects().  Returns (counts, residue): counts (nboards, npat)
+        uint32, residue (nboards,) uint32; with counts=False or residue=False that output is None and
+        its work is skipped (not both).
+
+        Cells: cell_i(x, y) is board i's cell; on a torus the coordinates are taken mod width and mod
+        height, on a plane a cell outside the rectangle is dead.  Match: pattern p matches board i at
+        anchor (x, y) when cell_i(x + c, y + r) == alive_p(r, c) for every (r, c) that p looks at.
+        Anchors: 0 <= x < width, 0 <= y < height on a torus; -(w - 1) <= x <= width - 1 and
+        -(h - 1) <= y <= height - 1 on a plane, so an object at the border, its dead ring outside,
+        is counted.  counts[i, p] is the number of matching anchors; overlapping matches each count.
+        residue[i] is the number of live cells of board i that no match covers, a match covering the
+        cells under its pattern's live cells: 0 means the list explains the whole board.  Without
+        patterns residue is alive_counts().  The result for board i depends on board i, the topology
+        and the patterns only, counts[:, p] on pattern p only, residue not on the patterns' order.
+        Nothing else moves: the boards, the turn, the rules, the records and the switches stay.
+
+        The workflow: (1) search() or search_exact(); (2) pick the seeds of interest; (3)
+        Batch(w, h, len(seeds)), init_random(seeds=seeds), step(the largest stop_turn); (4)
+        census(...).  An oscillating ash is seen in the phase of the turn the batch is at, which is
+        why common_objects() lists oscillators in every phase.
+
+        A bad pattern raises GolHipError(ERR_ARG) naming its index: an array before any device work,
+        a Pattern (and a pattern larger than the board, or more than 256) from the library."""
+        pats = []
+        for i, p in enumerate(patterns):
+            if isinstance(p, Pattern):
+                pats.append(p)
+                continue
+            try:
+                pats.append(pattern(p))
+            except GolHipError as e:
+                raise GolHipError(e.code, f"pattern {i}: " + str(e).split(": ", 2)[2])
+        npat = len(pats)
+        table = (Pattern * max(npat, 1))(*pats)
+        c = np.zeros((self.nboards, npat), dtype=np.uint32) if counts else None
+        r = np.zeros(self.nboards, dtype=np.uint32) if residue else None
+        self._check(self._L.golhip_batch_census(self._h, ctypes.addressof(table) if npat else None, npat,
+                                                c.ctypes.data if counts else None,
+                                                r.ctypes.data if residue else None))
+        return c, r
 
     @property
     def turn(self) -> int:

@@ -418,8 +418,9 @@ int golhip_edge_wait(golhip_t h, double *total_ms, int64_t *blocks);
  *     first golhip_batch_track_period(b, 1) (a second boards-sized buffer, the snapshots, and one
  *     int64 per board), the first golhip_batch_set_rules and the first golhip_batch_search or
  *     golhip_batch_search_exact (one chunk's seeds, rule pairs, records and cycle starts: 3.5 MiB)
- *     allocates device memory: bytes, seeds, rules, counts and history go through a transfer stage
- *     in chunks.
+ *     and the first golhip_batch_census (the pattern table: 66 KiB)
+ *     allocates device memory: bytes, seeds, rules, counts, history and the census's results go
+ *     through a transfer stage in chunks.
  *   - A batch has ONE turn counter.  Any golhip_batch_load_bytes, even of part of the batch, and any
  *     golhip_batch_init_random set it to 0 and clear every settle and period record: a batch is filled, then run.
  *   - golhip_batch_init_random: board i is bit for bit what golhip_init_random(seed_i, density_q32)
@@ -611,6 +612,49 @@ int golhip_batch_set_topology(golhip_batch_t b, int topology);
 int golhip_batch_get_topology(golhip_batch_t b, int *topology);
 int golhip_batch_set_soup_box(golhip_batch_t b, int box_w, int box_h); /* 0, 0: the whole board (default) */
 int golhip_batch_get_soup_box(golhip_batch_t b, int *box_w, int *box_h);
+/* The census: what the boards hold, by pattern matching on the device.  A search record says when a
+ * soup settled, with what period and how many cells; the census says into what: how many blocks,
+ * beehives, blinkers, gliders ... are on each board, and how many live cells belong to none of the
+ * listed objects.  A board with residue 0 is fully explained; anything else is worth a look.  One
+ * workgroup per board (gol_batch_census) stages the board in LDS and matches every pattern at every
+ * anchor, 32 anchors per lane.
+ *   - Cells.  cell_i(x, y) is board i's cell.  On a torus the coordinates are taken mod width and mod
+ *     height.  On a plane (golhip_batch_set_topology) a cell outside the rectangle is dead.
+ *   - Match.  Pattern p matches board i at anchor (x, y) when cell_i(x + c, y + r) == alive_p(r, c) for
+ *     every (r, c) in care_p.  Cells outside care_p are not looked at.
+ *   - Anchors.  On a torus: 0 <= x < width, 0 <= y < height.  On a plane: -(w - 1) <= x <= width - 1
+ *     and -(h - 1) <= y <= height - 1.  Every pattern has a live cell, so every match overlaps the
+ *     board.  An object touching the plane's border, with its dead ring outside, is counted.
+ *   - Counts.  counts[i * npat + p] is the number of matching anchors.  Overlapping matches each count.
+ *   - Residue.  residue[i] is the number of live cells of board i not covered by any match.  A match
+ *     (p, x, y) covers the cells (x + c, y + r) with alive_p(r, c) set, wrapped on a torus.  With
+ *     npat == 0, residue is golhip_batch_alive_counts's result and counts is not touched.
+ *   - Bad arguments.  The following are GOLHIP_ERR_ARG; the text names the pattern index and the
+ *     offence, and the handle and outputs stay untouched: npat < 0 or npat > 256; patterns == NULL with
+ *     npat > 0; both outputs NULL; w or h outside 1..32; w > width or h > height; a bit at column >= w,
+ *     or in a row >= h; alive not a subset of care; a pattern without a live cell.
+ *   - No side effects.  The call reads the boards as they are at the current turn.  It changes
+ *     nothing: boards, turn, rule(s), settle, period and search records, switches, topology and box
+ *     all stay as they were.  It is legal with tracking on or off and at any turn.  The rule plays no
+ *     part.
+ *   - Independence.  The result for board i depends on board i, the topology and the pattern list
+ *     only.  It does not depend on nboards, on how boards are cut into launches, or on
+ *     GOLHIP_STAGE_BYTES.  counts[.., p] does not depend on the other patterns.  residue does not
+ *     depend on their order.
+ *   - An oscillating ash is seen in the phase of the turn the batch is at: list an oscillator in
+ *     every phase.  Either output may be NULL, not both; a NULL residue skips the cover work.
+ *   - Boards go out in launches of at most 65536 boards; counts and residues come back through the
+ *     transfer stage in chunks.  The pattern table lives in device memory (66 KiB) allocated by the
+ *     first golhip_batch_census, the sixth and last allocating call of the list above, and freed by
+ *     golhip_batch_destroy. */
+typedef struct {
+    int32_t  w, h;        /* 1..32 each */
+    uint32_t alive[32];   /* row r, bit c set: cell (r, c) must be alive */
+    uint32_t care[32];    /* row r, bit c set: cell (r, c) is looked at; alive is a subset of care */
+} golhip_pattern_t;       /* 264 bytes */
+int golhip_batch_census(golhip_batch_t b, const golhip_pattern_t *patterns, int npat,
+                        uint32_t *counts  /* nboards * npat, or NULL */,
+                        uint32_t *residue /* nboards, or NULL */);
 
 #ifdef __cplusplus
 }

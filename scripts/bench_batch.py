@@ -61,6 +61,14 @@ repeat_turn, and the generations the pass adds (floor + period + 2 (cycle_start 
 over the soups that repeated) over the sum of repeat_turn and over the sum of stop_turn, the
 generations the search itself ran: the ratio the time ratio should track.
 
+--census: the census (Batch.census, gol_batch_census) instead of the run above.  --batches boards (4096
+and 65536 by default) of 64 x 64, seeds 0 .. B - 1 at density 1/2, stepped 2000 turns on the torus, and
+the 33 arrays of common_objects().  Before anything is timed counts and residue must equal a numpy
+brute force of the definitions on the first 64 boards.  Timed: (a) the only route there was,
+store() of every board, alone, and with the brute force's time on the 64-board sample scaled to B
+boards added; (b) one census call, with the residue and without.  One search call on the same seeds
+and the 2000-turn step are timed once each, for scale.
+
 One JSON line on stdout; --out also writes it to a file.  There is no CPU fallback: without a GPU
 the script fails.
 """
@@ -296,6 +304,77 @@ def exact_leg(a, res):
         print(json.dumps(row), file=sys.stderr, flush=True)
 
 
+def census_reference(board, patterns, plane=False):
+    """(counts, residue) of one board from the definitions of golhip_batch_census in numpy: the route
+    a host has without the call, after store()."""
+    a = board != 0
+    H, W = a.shape
+    big = np.pad(a, 31) if plane else np.tile(a, (1 + -(-31 // H), 1 + -(-31 // W)))
+    counts, covered = np.zeros(len(patterns), dtype=np.uint32), np.zeros((H, W), dtype=bool)
+    for k, p in enumerate(patterns):
+        h, w = p.shape
+        ny, nx, oy, ox = (H + h - 1, W + w - 1, 32 - h, 32 - w) if plane else (H, W, 0, 0)
+        m = np.ones((ny, nx), dtype=bool)
+        for r, c in zip(*np.nonzero(p >= 0)):
+            m &= big[oy + r:oy + r + ny, ox + c:ox + c + nx] == (p[r, c] == 1)
+        counts[k] = m.sum()
+        for y, x in zip(*np.nonzero(m)):
+            for r, c in zip(*np.nonzero(p == 1)):
+                covered[(y + oy - 31 * plane + r) % H, (x + ox - 31 * plane + c) % W] = True
+    return counts, int((a & ~covered).sum())
+
+
+def census_leg(a, res):
+    """Batch.census beside the only route there was before it (store() and matching on the host) and
+    beside the search that produced the soups, in this process."""
+    res["bench"] = "batch_census"
+    res["turns"] = CENSUS_TURNS
+    objs = golhip.common_objects()
+    pats = [p for v in objs.values() for p in v]
+    names = [k for k, v in objs.items() for _ in v]
+    res["patterns"] = len(pats)
+    sample = 64
+    for B in ([int(v) for v in a.batches.split(",")] if a.batches else [4096, 65536]):
+        seeds = np.arange(B, dtype=np.uint64)
+        with golhip.Batch(64, 64, B) as b:
+            t0 = time.perf_counter()
+            rec = b.search(B, seeds=seeds, max_turns=CENSUS_TURNS)
+            search_s = time.perf_counter() - t0
+            b.init_random(seeds=seeds)
+            t0 = time.perf_counter()
+            b.step(CENSUS_TURNS)
+            step_s = time.perf_counter() - t0
+            counts, residue = b.census(pats)
+            head = b.store(0, sample)
+            t0 = time.perf_counter()
+            want = [census_reference(board, pats) for board in head]
+            ref_s = time.perf_counter() - t0
+            assert np.array_equal(counts[:sample], np.array([w[0] for w in want])), B
+            assert np.array_equal(residue[:sample], np.array([w[1] for w in want])), B
+            assert np.array_equal(b.census(pats, residue=False)[0], counts), B
+            out = np.empty((B, 64, 64), dtype=np.uint8)
+            store_med, store_min = median_s(lambda: b.store(out=out), 2, a.calls)
+            both_med, both_min = median_s(lambda: b.census(pats), 2, a.calls)
+            cnt_med, cnt_min = median_s(lambda: b.census(pats, residue=False), 2, a.calls)
+        totals = {k: int(sum(int(counts[:, i].sum()) for i, n in enumerate(names) if n == k)) for k in objs}
+        host_s = store_med + ref_s * B / sample
+        row = {"width": 64, "height": 64, "boards": B, "totals": totals,
+               "boards_with_residue_0": int((residue == 0).sum()), "soups_with_a_repeat": int((rec["repeat_turn"] > 0).sum()),
+               "store_ms_median": round(store_med * 1e3, 3), "store_ms_min": round(store_min * 1e3, 3),
+               "reference_ms_per_board": round(ref_s / sample * 1e3, 3), "host_route_ms_scaled": round(host_s * 1e3, 1),
+               "census_ms_median": round(both_med * 1e3, 3), "census_ms_min": round(both_min * 1e3, 3),
+               "census_counts_only_ms_median": round(cnt_med * 1e3, 3), "census_counts_only_ms_min": round(cnt_min * 1e3, 3),
+               "census_boards_per_s": round(B / both_med, 1), "store_over_census": round(store_med / both_med, 2),
+               "host_route_over_census": round(host_s / both_med, 1),
+               "search_ms_once": round(search_s * 1e3, 3), "step_ms_once": round(step_s * 1e3, 3),
+               "census_over_search": round(both_med / search_s, 4)}
+        res["shapes"].append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+
+
+CENSUS_TURNS = 2000
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=7)
@@ -313,9 +392,21 @@ def main():
     ap.add_argument("--box", help="--plane: the soup box, e.g. 16x16")
     ap.add_argument("--max-turns", type=int, help="--plane, --exact: instead of the cases' max_turns")
     ap.add_argument("--exact", action="store_true", help="search_exact beside search (see above)")
+    ap.add_argument("--census", action="store_true", help="Batch.census beside store() + numpy (see above)")
     a = ap.parse_args()
     assert a.calls >= 7
     assert a.rule or not a.per_board_rules, "--per-board-rules needs --rule"
+    if a.census:
+        assert not (a.exact or a.plane or a.search or a.period or a.rule), "--census replaces the other legs"
+        res = {"bench": "batch_census", "version": golhip.load_library().golhip_version(), "turns": None,
+               "calls": a.calls, "shapes": []}
+        census_leg(a, res)
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            a.out.parent.mkdir(parents=True, exist_ok=True)
+            a.out.write_text(line + "\n")
+        return
     if a.exact:
         assert not (a.plane or a.search or a.period or a.rule), "--exact has its own rules and replaces the other legs"
         res = {"bench": "batch_cycle", "version": golhip.load_library().golhip_version(), "turns": None,
