@@ -37,8 +37,8 @@
 // advances once per generation.
 //
 // The exchange array.  A and B share ONE ex[2][NSEG + 1][4][16]; every board_gen call of the kernel,
-// whichever board it steps, takes the parity opposite to the call before it (par ^= 1 per call: in
-// the lockstep A and B alternate).  board_common.hpp's double-buffer argument speaks of consecutive
+// whichever board it steps, takes the parity opposite to the call before it (the call's index
+// mod 2, from the loop counters: in the lockstep A and B alternate).  board_common.hpp's double-buffer argument speaks of consecutive
 // CALLS, not of generations of one board, so it holds as it stands: call k writes ex[par], passes
 // ONE barrier and reads ex[par]; a wave that is a call ahead writes ex[par ^ 1]; it reaches call
 // k + 2's writes of ex[par] only through call k + 1's barrier, which no wave passes before every
@@ -58,7 +58,8 @@
 // left a loop an iteration earlier or later than the others would hang the workgroup.
 //   - The trip counts lo, period and n = s - lo + 1 come from the soup's record, loaded at an
 //     address that depends on blockIdx.x only: wave-uniform and the same in every wave.  A soup
-//     without a repeat, and one with s == 0, returns before its first barrier, in every wave.
+//     without a repeat, and one with s == 0 (unless an ash buffer is set: the ash hand-off below),
+//     returns before its first barrier, in every wave.
 //   - The points at which `stop` is read are a function of the index i alone.
 //   - Every wave reads the same value there.  `stop` is written by thread 0 at the start (0, before
 //     the first barrier; the first read follows at least two barriers) and by wave 0 in take_mask
@@ -79,6 +80,31 @@
 //     pm[k & 1] more than 60 barriers after wave 0 read it, and the two takes at the end are of
 //     adjacent blocks.
 // cycle_start = lo + the first index, stored by lane 0 of wave 0 with an ordinary store.
+//
+// The ash hand-off (golhip_batch_search_census).  With cp.ash set the workgroup also stores a board
+// that lies on the soup's cycle, for the census that follows on the same stream, and its turn:
+//   - a soup that repeated, s > 0: board A as it leaves the lockstep -- by the flag or by the closing
+//     compare -- at turn T = the generations A has run: lo + period alone, then one per lockstep
+//     index whose step ran.  A was seeded at drift 0 and drifts one bit east per generation, so the
+//     rows go back to the board frame as gol_plane_rule's and gol_batch_period's do: unrotate16(a[r],
+//     lane, T & 511), one copy of the replicated row stored by the lanes c16 < wd.  Z plays no part.
+//     cycle_start <= lo + first < T on the flag exit and T = repeat_turn on the closing compare; the
+//     loop stops before index n - 1, so T <= lo + period + n - 1 = repeat_turn either way: board T
+//     is on the cycle and no generation beyond repeat_turn has run.  T is a function of the record
+//     and of cycle_start alone: the flag exit is at index 32 (first / 32) + 33 if that is below
+//     n - 1, the closing compare otherwise.  The ash is NOT phase-aligned to cycle_start: that would
+//     take another inlined copy of the step.
+//   - s <= 0 (board(0) is on the cycle): the seeded board, T = 0.  The early return is taken only
+//     without an ash buffer; with one the workgroup runs on with every trip count zero (no solo
+//     generation, no lockstep iteration), the closing compare finds A == B = board(0) and gives
+//     cycle_start = 0, and the store site below is the only one.
+//   - no repeat: ash_turn = -1 and no row; the host has zeroed the chunk's buffer.
+// cp.ash is a kernel argument, workgroup-uniform: whether the s <= 0 workgroup returns early (before
+// its first barrier, in every wave) or runs on (through the closing compare's ONE barrier, in every
+// wave) is the same in all its waves.  The tail itself has no barrier: it comes after the last
+// one, adds one ds_bpermute pair and one store per row, and every wave reaches it with the same T
+// (solo, i and the exit taken are wave-uniform and the same in every wave, see above).  With
+// cp.ash null the kernel writes what it always wrote.
 //
 // Functors: LifeNext for a uniform B3/S23, RuleNext<RuleTable> for every other rule, per-soup rules
 // included: 8 shapes x 2 kernels.  A catalogue rule (HighLife, ...) whose search ran constant-folded
@@ -101,17 +127,26 @@ __global__ __launch_bounds__(64 * W) void gol_batch_cycle(BatchCycleParams cp) {
     const int rep = __builtin_amdgcn_readfirstlane((int)sp.out[blockIdx.x].repeat_turn);  // <= 2^20
     const int period = __builtin_amdgcn_readfirstlane((int)sp.out[blockIdx.x].period);
     if (rep < 0) {
-        if (threadIdx.x == 0) cp.cycle_start[blockIdx.x] = -1;
+        if (threadIdx.x == 0) {
+            cp.cycle_start[blockIdx.x] = -1;
+            if (cp.ash) cp.ash_turn[blockIdx.x] = -1;  // no ash: the host has zeroed the chunk
+        }
         return;
     }
     const int s = rep - period;  // the snapshot turn 2^j - 1
-    if (s <= 0) {
+    // board(0) is on the cycle: nothing runs.  Without an ash buffer the workgroup leaves here, as it
+    // always did; with one (a kernel argument: the same in every wave) it goes on with every trip
+    // count zero, seeds board(0) below, finds it equal to itself in the closing compare and stores
+    // it at the one store site, turn 0.
+    const bool still = s <= 0;
+    if (still && !cp.ash) {
         if (threadIdx.x == 0) cp.cycle_start[blockIdx.x] = 0;
         return;
     }
     const int half = (s + 1) >> 1;                // 2^(j-1)
     const int lo = period <= half ? half - 1 : 0;  // cycle_start_floor
-    const int n = s - lo + 1;                      // lockstep compares: turns lo .. s
+    const int solo = still ? 0 : lo + period;     // A's generations before the lockstep
+    const int n = still ? 1 : s - lo + 1;          // lockstep compares: turns lo .. s
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int c16 = lane & 15;
@@ -139,13 +174,14 @@ __global__ __launch_bounds__(64 * W) void gol_batch_cycle(BatchCycleParams cp) {
                box_word_mask(sg * R + r, c16 & (wd - 1), sp.width, cp.bp.box);
     const int up = sg == 0 ? (plane ? NSEG : NSEG - 1) : sg - 1;
     const int dn = sg == NSEG - 1 ? (plane ? NSEG : 0) : sg + 1;
-    int par = 0;  // the exchange buffer of the next board_gen call, A's or B's
-    // one generation of board x under seam mask z (advanced in place)
-    auto gen = [&](uint32_t(&x)[R], uint32_t &z) {
+    // one generation of board x under seam mask z (advanced in place) through exchange buffer par:
+    // call k of the kernel, whichever board it steps, takes par = k & 1.  The callers derive it from
+    // their loop counters; carried from call to call in a variable of its own it was moved to the
+    // vector unit once the ash tail stood behind the loops, a v_mul_lo_u32 per call for ex[par].
+    auto gen = [&](uint32_t(&x)[R], uint32_t &z, int par) {
         uint32_t sm[R], cy[R], ctr[R], nx[R];
         sums16_plane<R>(x, z, sm, cy, ctr);
         board_gen<R>(sm, cy, ctr, ex, par, sg, up, dn, c16, next, nx);
-        par ^= 1;
 #pragma unroll
         for (int r = 0; r < R; ++r) x[r] = nx[r];
     };
@@ -155,12 +191,12 @@ __global__ __launch_bounds__(64 * W) void gol_batch_cycle(BatchCycleParams cp) {
 #pragma unroll
     for (int r = 0; r < R; ++r) b[r] = a[r];
 #pragma clang loop unroll(disable)
-    for (int g = 0; g < lo + period; ++g) {
+    for (int g = 0; g < solo; ++g) {
         if (g == lo) {
 #pragma unroll
             for (int r = 0; r < R; ++r) b[r] = a[r];
         }
-        gen(a, Z);
+        gen(a, Z, g & 1);
         if (g >= lo) {
             uint32_t wl[R];
 #pragma unroll
@@ -216,7 +252,7 @@ __global__ __launch_bounds__(64 * W) void gol_batch_cycle(BatchCycleParams cp) {
 #pragma clang loop unroll(disable)
         for (int h = 0; h < 2; ++h) {
             zn = Z;
-            gen(a, zn);
+            gen(a, zn, (solo ^ h) & 1);  // two calls per index: the parity the solo loop left, then the other
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const uint32_t t = a[r];
@@ -249,6 +285,27 @@ __global__ __launch_bounds__(64 * W) void gol_batch_cycle(BatchCycleParams cp) {
         take_mask(last);
     }
     if (threadIdx.x == 0) cp.cycle_start[blockIdx.x] = first >= 0 ? (int64_t)lo + first : -1;
+    // The ash: board A as it left the lockstep, back in the board frame.  A has run `solo` generations
+    // alone and one per lockstep index passed: i of them when the loop ran out (the closing compare
+    // steps nothing), i + 1 when the flag ended it behind index i's step.
+    if (cp.ash) {
+        const int T = __builtin_amdgcn_readfirstlane(solo + i + (retired ? 1 : 0));
+        // The tail's lane arithmetic starts from a thread index the compiler cannot see through: taken
+        // from lane, c16 and sg above it is loop-invariant, and its addresses were computed before the
+        // loops and held in registers through them (the (16, 8) kernels went from 59 to 71 VGPRs and
+        // from 8 to 7 waves per SIMD: one workgroup per CU instead of two).
+        int tid = (int)threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        const int tl = tid & 63, tc = tid & 15, ts = tid >> 4;  // lane, c16, sg
+        const bool own = tc < wd;  // one copy of the replicated row is stored
+        uint32_t *__restrict__ board = cp.ash + (int64_t)blockIdx.x * (NSEG * R) * wd;  // board_pitch: height * wd
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const uint32_t v = unrotate16(a[r], tl, T & 511);
+            if (own) board[(ts * R + r) * wd + tc] = v;
+        }
+        if (threadIdx.x == 0) cp.ash_turn[blockIdx.x] = T;
+    }
 }
 
 // Every shape of the table under one functor.

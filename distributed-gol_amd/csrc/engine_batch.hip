@@ -27,7 +27,10 @@
 // at most 2^44 cell updates, so that no launch runs long on a shared device.
 // golhip_batch_search_exact is the same call with a second pass per chunk, gol_batch_cycle
 // (batch_cycle.hpp), which turns each record's (repeat_turn, period) into the soup's cycle_start, the
-// first turn of its cycle; launch_batch_cycle below picks its functor.
+// first turn of its cycle; launch_batch_cycle below picks its functor.  golhip_batch_search_census is
+// the exact call whose pass also stores, per soup, a board on the soup's cycle into a chunk-sized
+// ash buffer (at most 64 MiB, allocated by the first such call), over which the census runs:
+// search_run has the order of a chunk.
 //
 // Device memory is allocated at create (the boards, the per-board counters, the transfer stage), by
 // the first golhip_batch_track_settle(b, 1) (board(t - 1) of every board), by the first
@@ -77,6 +80,11 @@ struct golhip_batch {
     uint32_t *search_rules = nullptr;
     golhip::SoupRecord *search_out = nullptr;
     int64_t *search_cycle = nullptr;  // golhip_batch_search_exact: the chunk's cycle starts
+    uint32_t *search_ash = nullptr;       // golhip_batch_search_census: one chunk's boards, at most 64 MiB
+    int64_t *search_ash_turn = nullptr;   // and their turns
+    uint8_t *search_stage = nullptr;      // and the stage their census and cells come back through
+    int64_t search_stage_bytes = 0;
+    int64_t stage_limit = 0;              // GOLHIP_STAGE_BYTES at create, 0 without: it caps that stage too
     golhip::CensusPattern *census_pat = nullptr;  // golhip_batch_census: the pattern table of a call
     int topology = GOLHIP_TOPOLOGY_TORUS;
     int box_w = 0, box_h = 0;  // the soup box of init_random and search; 0, 0: the whole board
@@ -124,6 +132,9 @@ void batch_free(golhip_batch_t b) {
     if (b->search_rules) (void)hipFree(b->search_rules);
     if (b->search_out) (void)hipFree(b->search_out);
     if (b->search_cycle) (void)hipFree(b->search_cycle);
+    if (b->search_ash) (void)hipFree(b->search_ash);
+    if (b->search_ash_turn) (void)hipFree(b->search_ash_turn);
+    if (b->search_stage) (void)hipFree(b->search_stage);
     if (b->census_pat) (void)hipFree(b->census_pat);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     b->boards = b->prev = b->rules = b->snap = nullptr;
@@ -134,6 +145,10 @@ void batch_free(golhip_batch_t b) {
     b->search_rules = nullptr;
     b->search_out = nullptr;
     b->search_cycle = nullptr;
+    b->search_ash = nullptr;
+    b->search_ash_turn = nullptr;
+    b->search_stage = nullptr;
+    b->search_stage_bytes = 0;
     b->census_pat = nullptr;
     b->stream = nullptr;
 }
@@ -153,7 +168,7 @@ int batch_alloc(golhip_batch_t b) {
     // create, shrinks it: tests force chunked transfers and several launches per history call);
     // never less than one byte row or one uint32 per board (a generation of history, the counts)
     int64_t cap = kStageBytes;
-    if (const char *e = std::getenv("GOLHIP_STAGE_BYTES")) cap = std::max<int64_t>(1, std::atoll(e));
+    if (const char *e = std::getenv("GOLHIP_STAGE_BYTES")) cap = b->stage_limit = std::max<int64_t>(1, std::atoll(e));
     const int64_t floor_bytes = std::max<int64_t>(b->width, 4 * (int64_t)b->nboards);
     b->stage_bytes = std::max<int64_t>(floor_bytes, std::min<int64_t>(cap, b->width * b->height * b->nboards));
     BHIPCHK(b, hipMalloc(&b->stage, (size_t)b->stage_bytes));
@@ -174,6 +189,37 @@ int boards_replaced(golhip_batch_t b) {
 // Boards [first, first + n) <-> host bytes, as one tall array of n * height byte rows cut into
 // chunks the stage holds; a chunk is copied in one piece where the host rows are dense, else one
 // 2-D copy per board it touches.
+// The route itself, for n boards of the batch layout at `base` through a stage of stage_bytes: the
+// batch's own boards through its stage (transfer), or the ash buffer of golhip_batch_search_census
+// through that call's own stage (store only).  The strides have been checked.
+int transfer_boards(golhip_batch_t b, uint32_t *base, int64_t n, uint8_t *host, size_t row_stride, size_t board_stride,
+                    bool to_device, uint8_t *stage, int64_t stage_bytes) {
+    const int64_t W = b->width, H = b->height;
+    const bool dense = row_stride == (size_t)W && board_stride == (size_t)(W * H);
+    const int64_t rows = n * H, cr = std::max<int64_t>(1, stage_bytes / W);
+    for (int64_t r0 = 0; r0 < rows; r0 += cr) {
+        const int64_t nr = std::min(cr, rows - r0);
+        uint32_t *dev = base + r0 * b->wd;
+        if (!to_device) BHIPCHK(b, launch_unpack(dev, b->wd, nr, W, stage, b->stream));
+        for (int64_t r = r0; r < r0 + nr;) {  // the chunk's rows, board by board
+            const int64_t bi = r / H, y = r - bi * H;
+            const int64_t m = dense ? nr : std::min(H - y, r0 + nr - r);
+            uint8_t *hp = host + (size_t)bi * board_stride + (size_t)y * row_stride;
+            uint8_t *sp = stage + (r - r0) * W;
+            if (to_device)
+                BHIPCHK(b, hipMemcpy2DAsync(sp, (size_t)W, hp, row_stride, (size_t)W, (size_t)m, hipMemcpyHostToDevice,
+                                            b->stream));
+            else
+                BHIPCHK(b, hipMemcpy2DAsync(hp, row_stride, sp, (size_t)W, (size_t)W, (size_t)m, hipMemcpyDeviceToHost,
+                                            b->stream));
+            r += m;
+        }
+        if (to_device) BHIPCHK(b, launch_pack(stage, nr, W, b->wd, dev, b->wd, b->stream));
+        BHIPCHK(b, hipStreamSynchronize(b->stream));
+    }
+    return GOLHIP_OK;
+}
+
 int transfer(golhip_batch_t b, int first, int n, uint8_t *host, size_t row_stride, size_t board_stride,
              bool to_device) {
     if (!host) return bfail(b, GOLHIP_ERR_ARG, "buffer is null");
@@ -185,29 +231,8 @@ int transfer(golhip_batch_t b, int first, int n, uint8_t *host, size_t row_strid
     if (board_stride < (size_t)(H - 1) * row_stride + (size_t)W)
         return bfail(b, GOLHIP_ERR_ARG, "board_stride %zu < the %lld rows of a board", board_stride, (long long)H);
     BHIPCHK(b, hipSetDevice(b->device));
-    const bool dense = row_stride == (size_t)W && board_stride == (size_t)(W * H);
-    const int64_t rows = (int64_t)n * H, cr = std::max<int64_t>(1, b->stage_bytes / W);
-    for (int64_t r0 = 0; r0 < rows; r0 += cr) {
-        const int64_t nr = std::min(cr, rows - r0);
-        uint32_t *dev = b->boards + (int64_t)first * b->board_words + r0 * b->wd;
-        if (!to_device) BHIPCHK(b, launch_unpack(dev, b->wd, nr, W, b->stage, b->stream));
-        for (int64_t r = r0; r < r0 + nr;) {  // the chunk's rows, board by board
-            const int64_t bi = r / H, y = r - bi * H;
-            const int64_t m = dense ? nr : std::min(H - y, r0 + nr - r);
-            uint8_t *hp = host + (size_t)bi * board_stride + (size_t)y * row_stride;
-            uint8_t *sp = b->stage + (r - r0) * W;
-            if (to_device)
-                BHIPCHK(b, hipMemcpy2DAsync(sp, (size_t)W, hp, row_stride, (size_t)W, (size_t)m, hipMemcpyHostToDevice,
-                                            b->stream));
-            else
-                BHIPCHK(b, hipMemcpy2DAsync(hp, row_stride, sp, (size_t)W, (size_t)W, (size_t)m, hipMemcpyDeviceToHost,
-                                            b->stream));
-            r += m;
-        }
-        if (to_device) BHIPCHK(b, launch_pack(b->stage, nr, W, b->wd, dev, b->wd, b->stream));
-        BHIPCHK(b, hipStreamSynchronize(b->stream));
-    }
-    return GOLHIP_OK;
+    return transfer_boards(b, b->boards + (int64_t)first * b->board_words, n, host, row_stride, board_stride, to_device,
+                           b->stage, b->stage_bytes);
 }
 
 // What the next step launches: 0 gol_batch (uniform B3/S23), 1 gol_batch_rule constant-folded, 2 its
@@ -247,6 +272,7 @@ hipError_t launch_batch_cycle(int W, int R, int nsoups, const BatchCycleParams &
     const BatchSearchParams &sp = cp.bp.s;
     const SoupBox &bx = cp.bp.box;
     if (sp.max_turns < 1 || sp.max_turns > kSearchMaxTurns || nsoups < 1 || !sp.out || !cp.cycle_start ||
+        (cp.ash && !cp.ash_turn) ||
         (sp.wd != 4 && sp.wd != 8 && sp.wd != 16) || sp.width < 64 || sp.width % 64 != 0 || sp.width > 32 * sp.wd ||
         (sp.width & (sp.width - 1)) != 0)
         return hipErrorInvalidValue;
@@ -586,10 +612,25 @@ int golhip_batch_get_rules(golhip_batch_t b, uint32_t *birth, uint32_t *survive)
 
 // golhip_batch_search (exact == false: cycle_start is not looked at) and golhip_batch_search_exact: the
 // same checks, chunks and search launches; the exact call adds gol_batch_cycle behind each chunk's
-// search launch and one more copy.
+// search launch and one more copy.  golhip_batch_search_census (sc set) is the exact call whose pass also
+// hands a board on each soup's cycle to the census, chunk by chunk in stream order: the search
+// launch, the chunk's ash zeroed, gol_batch_cycle with the ash buffer, the census over that buffer,
+// the ash unpacked if it is asked for.
+struct SearchCensus {
+    const golhip_pattern_t *patterns;
+    int npat;
+    int64_t *ash_turn;
+    uint32_t *counts, *residue;
+    uint8_t *ash_cells;
+};
+constexpr int64_t kAshBytes = (int64_t)64 << 20;  // the ash buffer of a chunk, at most
+static int census_check(golhip_batch_t b, const golhip_pattern_t *patterns, int npat);
+static int census_boards(golhip_batch_t b, const uint32_t *base, int64_t nboards, int npat, uint32_t *counts,
+                         uint32_t *residue, uint32_t *stage, int64_t cap);
+
 static int search_run(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds, uint64_t seed0, uint32_t density_q32,
                       int64_t max_turns, const uint32_t *birth, const uint32_t *survive, golhip_soup_t *out,
-                      int64_t *cycle_start, bool exact) {
+                      int64_t *cycle_start, bool exact, const SearchCensus *sc = nullptr) {
     if (!b) return GOLHIP_ERR_ARG;
     if (b->width % 64 != 0)
         return bfail(b, GOLHIP_ERR_ARG, "search needs width %% 64 == 0, as init_random (width %lld)", (long long)b->width);
@@ -605,9 +646,22 @@ static int search_run(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds, u
                              "has 8 neighbours)", (long long)i, birth[i], survive[i]);
         }
     }
+    if (sc) {  // the census's checks, in golhip_batch_census's words
+        if (sc->npat < 0 || sc->npat > kCensusMaxPatterns)
+            return bfail(b, GOLHIP_ERR_ARG, "census npat %d: 0 to %d patterns", sc->npat, kCensusMaxPatterns);
+        if (sc->npat > 0 && !sc->patterns)
+            return bfail(b, GOLHIP_ERR_ARG, "census patterns is null with npat %d", sc->npat);
+        if (!sc->counts && !sc->residue && !sc->ash_cells)
+            return bfail(b, GOLHIP_ERR_ARG, "census counts, residue and ash_cells are all null");
+        if (sc->counts && sc->npat == 0)
+            return bfail(b, GOLHIP_ERR_ARG, "census npat 0 with counts: counts has no columns, pass null");
+        const int rc = census_check(b, sc->patterns, sc->npat);
+        if (rc) return rc;
+    }
     if (nsoups == 0) return GOLHIP_OK;
     if (!out) return bfail(b, GOLHIP_ERR_ARG, "out is null");
     if (exact && !cycle_start) return bfail(b, GOLHIP_ERR_ARG, "cycle_start is null");
+    if (sc && !sc->ash_turn) return bfail(b, GOLHIP_ERR_ARG, "ash_turn is null");
     static_assert(sizeof(golhip_soup_t) == 32 && sizeof(SoupRecord) == 32, "a soup's record is 32 bytes");
     static_assert(offsetof(golhip_soup_t, repeat_turn) == offsetof(SoupRecord, repeat_turn) &&
                       offsetof(golhip_soup_t, period) == offsetof(SoupRecord, period) &&
@@ -621,8 +675,37 @@ static int search_run(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds, u
     if (!b->search_out) BHIPCHK(b, hipMalloc(&b->search_out, sizeof(SoupRecord) * (size_t)kSearchChunk));
     if (!b->search_cycle) BHIPCHK(b, hipMalloc(&b->search_cycle, sizeof(int64_t) * (size_t)kSearchChunk));
     // a chunk: at most kSearchChunk soups and at most 2^44 cell updates if no soup repeats, at least 1
-    const int64_t chunk = std::max<int64_t>(
+    int64_t chunk = std::max<int64_t>(
         1, std::min<int64_t>(kSearchChunk, kSearchChunkUpdates / (b->width * b->height * max_turns)));
+    if (sc) {  // and no more soups than the ash buffer holds boards: 64 MiB, at least one board
+        const int64_t board_bytes = (int64_t)sizeof(uint32_t) * b->board_words;
+        const int64_t ash_boards = std::max<int64_t>(1, std::min<int64_t>(kSearchChunk, kAshBytes / board_bytes));
+        if (!b->search_ash) BHIPCHK(b, hipMalloc(&b->search_ash, (size_t)(ash_boards * board_bytes)));
+        if (!b->search_ash_turn) BHIPCHK(b, hipMalloc(&b->search_ash_turn, sizeof(int64_t) * (size_t)kSearchChunk));
+        chunk = std::min(chunk, ash_boards);
+        // The chunk's results come back through a stage of the call's own, not the batch's, which is sized
+        // by nboards and a search runs on a batch of one board: a chunk's counts and residues, and
+        // its cells if they are asked for, at most 64 MiB; it only grows.
+        const int64_t most = std::min(chunk, nsoups);
+        int64_t need = 4 * most * ((sc->counts ? sc->npat : 0) + 1);
+        if (sc->ash_cells) need = std::max(need, most * b->width * b->height);
+        need = std::min(need, kAshBytes);
+        // the test hook shrinks this stage as it shrinks the batch's: never below a byte row or a uint32
+        if (b->stage_limit) need = std::min(need, std::max<int64_t>(b->stage_limit, std::max<int64_t>(b->width, 4)));
+        if (need > b->search_stage_bytes) {
+            if (b->search_stage) BHIPCHK(b, hipFree(b->search_stage));
+            b->search_stage = nullptr;
+            b->search_stage_bytes = 0;
+            BHIPCHK(b, hipMalloc(&b->search_stage, (size_t)need));
+            b->search_stage_bytes = need;
+        }
+        if (sc->npat > 0 && (sc->counts || sc->residue)) {
+            if (!b->census_pat)
+                BHIPCHK(b, hipMalloc(&b->census_pat, sizeof(CensusPattern) * (size_t)kCensusMaxPatterns));
+            BHIPCHK(b, hipMemcpyAsync(b->census_pat, sc->patterns, sizeof(CensusPattern) * (size_t)sc->npat,
+                                      hipMemcpyHostToDevice, b->stream));
+        }
+    }
     BatchSearchParams sp{};
     sp.density = density_q32;
     sp.wd = b->wd;
@@ -660,10 +743,49 @@ static int search_run(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds, u
         BHIPCHK(b, hipMemcpyAsync(out + i, b->search_out, sizeof(SoupRecord) * (size_t)n, hipMemcpyDeviceToHost,
                                   b->stream));
         if (exact) {  // the second pass reads the chunk's records on the device (stream order)
-            const BatchCycleParams cp{{sp, soup_box(b), b->topology == GOLHIP_TOPOLOGY_PLANE ? 1 : 0}, b->search_cycle};
+            BatchCycleParams cp{{sp, soup_box(b), b->topology == GOLHIP_TOPOLOGY_PLANE ? 1 : 0}, b->search_cycle};
+            if (sc) {  // a soup without a repeat writes no row: its ash is the empty board
+                BHIPCHK(b, hipMemsetAsync(b->search_ash, 0, sizeof(uint32_t) * (size_t)(n * b->board_words), b->stream));
+                cp.ash = b->search_ash;
+                cp.ash_turn = b->search_ash_turn;
+            }
             BHIPCHK(b, launch_batch_cycle(b->W, b->R, (int)n, cp, b->stream));
             BHIPCHK(b, hipMemcpyAsync(cycle_start + i, b->search_cycle, sizeof(int64_t) * (size_t)n,
                                       hipMemcpyDeviceToHost, b->stream));
+        }
+        if (sc) {
+            BHIPCHK(b, hipMemcpyAsync(sc->ash_turn + i, b->search_ash_turn, sizeof(int64_t) * (size_t)n,
+                                      hipMemcpyDeviceToHost, b->stream));
+            uint32_t *res = sc->residue ? sc->residue + i : nullptr;
+            if (sc->npat > 0 && (sc->counts || res)) {
+                const int rc = census_boards(b, b->search_ash, n, sc->npat,
+                                             sc->counts ? sc->counts + i * sc->npat : nullptr, res,
+                                             reinterpret_cast<uint32_t *>(b->search_stage), b->search_stage_bytes / 4);
+                if (rc) return rc;
+            } else if (res) {  // no pattern: nothing is covered, the residue is the ash's live cells
+                uint32_t *d = reinterpret_cast<uint32_t *>(b->search_stage);
+                const int64_t cb = std::max<int64_t>(1, b->search_stage_bytes / 4);
+                for (int64_t j = 0; j < n; j += cb) {
+                    const int64_t nb = std::min<int64_t>(cb, n - j);
+                    BHIPCHK(b, launch_batch_popcount(b->search_ash + j * b->board_words, b->board_words, nb, b->height,
+                                                     b->width, b->wd, d, b->stream));
+                    BHIPCHK(b, hipMemcpyAsync(res + j, d, sizeof(uint32_t) * (size_t)nb, hipMemcpyDeviceToHost, b->stream));
+                    BHIPCHK(b, hipStreamSynchronize(b->stream));  // the next launch rewrites the stage
+                }
+            }
+            if (sc->ash_cells) {
+                const size_t cells = (size_t)(b->width * b->height);
+                uint8_t *bytes = sc->ash_cells + (size_t)i * cells;
+                const int rc = transfer_boards(b, b->search_ash, n, bytes, (size_t)b->width, cells, false,
+                                               b->search_stage, b->search_stage_bytes);
+                if (rc) return rc;
+                for (size_t k = 0; k < (size_t)n * cells; ++k) bytes[k] &= 1;  // the unpack kernel's 255 -> 1
+            }
+            BHIPCHK(b, hipStreamSynchronize(b->stream));
+            // a soup without a repeat: its cells are alive and none is explained
+            if (res)
+                for (int64_t j = 0; j < n; ++j)
+                    if (out[i + j].repeat_turn < 0) res[j] = out[i + j].population;
         }
         BHIPCHK(b, hipStreamSynchronize(b->stream));  // the next chunk rewrites the buffers (and `pairs`)
     }
@@ -679,6 +801,14 @@ int golhip_batch_search_exact(golhip_batch_t b, int64_t nsoups, const uint64_t *
                               uint32_t density_q32, int64_t max_turns, const uint32_t *birth, const uint32_t *survive,
                               golhip_soup_t *out, int64_t *cycle_start) {
     return search_run(b, nsoups, seeds, seed0, density_q32, max_turns, birth, survive, out, cycle_start, true);
+}
+
+int golhip_batch_search_census(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds, uint64_t seed0,
+                               uint32_t density_q32, int64_t max_turns, const uint32_t *birth, const uint32_t *survive,
+                               const golhip_pattern_t *patterns, int npat, golhip_soup_t *out, int64_t *cycle_start,
+                               int64_t *ash_turn, uint32_t *counts, uint32_t *residue, uint8_t *ash_cells) {
+    const SearchCensus sc{patterns, npat, ash_turn, counts, residue, ash_cells};
+    return search_run(b, nsoups, seeds, seed0, density_q32, max_turns, birth, survive, out, cycle_start, true, &sc);
 }
 
 // The checks of golhip_batch_census's pattern list; the text names the pattern index and the offence.
@@ -708,6 +838,64 @@ static int census_check(golhip_batch_t b, const golhip_pattern_t *patterns, int 
     return GOLHIP_OK;
 }
 
+// The census of `nboards` boards of the batch layout at `base` -- the batch's own, or one chunk of
+// golhip_batch_search_census's ash -- under the patterns already in b->census_pat (npat >= 1).  counts
+// (nboards x npat) and residue (nboards) are host memory, either may be null.  The results come back
+// through `stage`, device memory of cap >= 1 words: the batch's transfer stage, or the search's own.
+static int census_boards(golhip_batch_t b, const uint32_t *base, int64_t nboards, int npat, uint32_t *counts,
+                         uint32_t *residue, uint32_t *stage, int64_t cap) {
+    BatchCensusParams cp{};
+    cp.board_pitch = b->board_words;
+    cp.wd = b->wd;
+    cp.width = (int32_t)b->width;
+    cp.height = (int32_t)b->height;
+    cp.plane = b->topology == GOLHIP_TOPOLOGY_PLANE ? 1 : 0;
+    // The results come back through the stage.  Where it holds a board's npat counts and its residue,
+    // one pass: chunks of boards, each launch writing both.  A smaller stage (GOLHIP_STAGE_BYTES) takes the
+    // counts in groups of patterns -- counts[.., p] does not depend on the other patterns -- and the
+    // residue in a pass of its own over the whole list.
+    const int64_t per_board = (counts ? npat : 0) + (residue ? 1 : 0);
+    const bool one_pass = per_board <= cap;
+    const int64_t pgroup = one_pass ? npat : std::min<int64_t>(npat, cap);
+    for (int64_t p0 = 0; counts && p0 < npat; p0 += pgroup) {
+        const int64_t np = std::min<int64_t>(pgroup, npat - p0);
+        const bool both = one_pass && residue;
+        const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(kSearchChunk, cap / (np + (both ? 1 : 0))));
+        for (int64_t i = 0; i < nboards; i += chunk) {
+            const int64_t n = std::min<int64_t>(chunk, nboards - i);
+            cp.boards = base + i * b->board_words;
+            cp.patterns = b->census_pat + p0;
+            cp.npat = (int32_t)np;
+            cp.counts = stage;
+            cp.residue = both ? stage + n * np : nullptr;
+            BHIPCHK(b, launch_batch_census((int)n, cp, b->stream));  // a missing kernel is an error
+            BHIPCHK(b, hipMemcpy2DAsync(counts + i * npat + p0, sizeof(uint32_t) * (size_t)npat, stage,
+                                        sizeof(uint32_t) * (size_t)np, sizeof(uint32_t) * (size_t)np, (size_t)n,
+                                        hipMemcpyDeviceToHost, b->stream));
+            if (both)
+                BHIPCHK(b, hipMemcpyAsync(residue + i, cp.residue, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost,
+                                          b->stream));
+            BHIPCHK(b, hipStreamSynchronize(b->stream));  // the next launch rewrites the stage
+        }
+    }
+    if (residue && !(counts && one_pass)) {
+        const int64_t chunk = std::min<int64_t>(kSearchChunk, cap);
+        for (int64_t i = 0; i < nboards; i += chunk) {
+            const int64_t n = std::min<int64_t>(chunk, nboards - i);
+            cp.boards = base + i * b->board_words;
+            cp.patterns = b->census_pat;
+            cp.npat = npat;
+            cp.counts = nullptr;
+            cp.residue = stage;
+            BHIPCHK(b, launch_batch_census((int)n, cp, b->stream));
+            BHIPCHK(b, hipMemcpyAsync(residue + i, stage, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, b->stream));
+            BHIPCHK(b, hipStreamSynchronize(b->stream));
+        }
+    }
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    return GOLHIP_OK;
+}
+
 int golhip_batch_census(golhip_batch_t b, const golhip_pattern_t *patterns, int npat, uint32_t *counts,
                         uint32_t *residue) {
     if (!b) return GOLHIP_ERR_ARG;
@@ -727,58 +915,9 @@ int golhip_batch_census(golhip_batch_t b, const golhip_pattern_t *patterns, int 
     if (!b->census_pat) BHIPCHK(b, hipMalloc(&b->census_pat, sizeof(CensusPattern) * (size_t)kCensusMaxPatterns));
     BHIPCHK(b, hipMemcpyAsync(b->census_pat, patterns, sizeof(CensusPattern) * (size_t)npat, hipMemcpyHostToDevice,
                               b->stream));
-    BatchCensusParams cp{};
-    cp.board_pitch = b->board_words;
-    cp.wd = b->wd;
-    cp.width = (int32_t)b->width;
-    cp.height = (int32_t)b->height;
-    cp.plane = b->topology == GOLHIP_TOPOLOGY_PLANE ? 1 : 0;
-    uint32_t *stage = reinterpret_cast<uint32_t *>(b->stage);
-    const int64_t cap = b->stage_bytes / 4;  // >= nboards >= 1 words
-    // The results come back through the stage.  Where it holds a board's npat counts and its residue,
-    // one pass: chunks of boards, each launch writing both.  A smaller stage (GOLHIP_STAGE_BYTES) takes the
-    // counts in groups of patterns -- counts[.., p] does not depend on the other patterns -- and the
-    // residue in a pass of its own over the whole list.
-    const int64_t per_board = (counts ? npat : 0) + (residue ? 1 : 0);
-    const bool one_pass = per_board <= cap;
-    const int64_t pgroup = one_pass ? npat : std::min<int64_t>(npat, cap);
-    for (int64_t p0 = 0; counts && p0 < npat; p0 += pgroup) {
-        const int64_t np = std::min<int64_t>(pgroup, npat - p0);
-        const bool both = one_pass && residue;
-        const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(kSearchChunk, cap / (np + (both ? 1 : 0))));
-        for (int64_t i = 0; i < b->nboards; i += chunk) {
-            const int64_t n = std::min<int64_t>(chunk, b->nboards - i);
-            cp.boards = b->boards + i * b->board_words;
-            cp.patterns = b->census_pat + p0;
-            cp.npat = (int32_t)np;
-            cp.counts = stage;
-            cp.residue = both ? stage + n * np : nullptr;
-            BHIPCHK(b, launch_batch_census((int)n, cp, b->stream));  // a missing kernel is an error
-            BHIPCHK(b, hipMemcpy2DAsync(counts + i * npat + p0, sizeof(uint32_t) * (size_t)npat, stage,
-                                        sizeof(uint32_t) * (size_t)np, sizeof(uint32_t) * (size_t)np, (size_t)n,
-                                        hipMemcpyDeviceToHost, b->stream));
-            if (both)
-                BHIPCHK(b, hipMemcpyAsync(residue + i, cp.residue, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost,
-                                          b->stream));
-            BHIPCHK(b, hipStreamSynchronize(b->stream));  // the next launch rewrites the stage
-        }
-    }
-    if (residue && !(counts && one_pass)) {
-        const int64_t chunk = std::min<int64_t>(kSearchChunk, cap);
-        for (int64_t i = 0; i < b->nboards; i += chunk) {
-            const int64_t n = std::min<int64_t>(chunk, b->nboards - i);
-            cp.boards = b->boards + i * b->board_words;
-            cp.patterns = b->census_pat;
-            cp.npat = npat;
-            cp.counts = nullptr;
-            cp.residue = stage;
-            BHIPCHK(b, launch_batch_census((int)n, cp, b->stream));
-            BHIPCHK(b, hipMemcpyAsync(residue + i, stage, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, b->stream));
-            BHIPCHK(b, hipStreamSynchronize(b->stream));
-        }
-    }
-    BHIPCHK(b, hipStreamSynchronize(b->stream));
-    return GOLHIP_OK;
+    // the batch's stage: >= nboards >= 1 words
+    return census_boards(b, b->boards, b->nboards, npat, counts, residue, reinterpret_cast<uint32_t *>(b->stage),
+                         b->stage_bytes / 4);
 }
 
 int golhip_batch_set_topology(golhip_batch_t b, int topology) {

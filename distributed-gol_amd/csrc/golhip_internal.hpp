@@ -434,9 +434,17 @@ hipError_t launch_plane_search_life(int W, int R, int nsoups, const BatchBoxSear
 // cycle_start[i]: the least t >= 0 with board(t + period) == board(t), -1 without a repeat.  Two
 // functors: B3/S23's rule step for a uniform B3/S23, the table form for everything else;
 // launch_batch_cycle (engine_batch.hip) checks the parameters and picks one.
+// With ash set (golhip_batch_search_census) the pass also hands over a board on each soup's cycle:
+// soup i's at ash + i * board_pitch in the batch layout (board_pitch = height * wd words, one copy
+// of each replicated row as the step kernels store it), and ash_turn[i] = the turn of that board:
+// cycle_start <= ash_turn <= repeat_turn; 0 with the seeded board for a soup that is on its cycle at
+// turn 0; -1, and no row written, for a soup without a repeat (the caller zeroes the buffer first).
+// With ash null the pass writes cycle_start only, as it always did, and ash_turn is not looked at.
 struct BatchCycleParams {
     BatchBoxSearchParams bp;
     int64_t *cycle_start;  // device memory, one per soup of the launch
+    uint32_t *ash;         // device memory, nsoups boards, or null
+    int64_t *ash_turn;     // device memory, one per soup of the launch; written whenever ash is set
 };
 hipError_t launch_batch_cycle(int W, int R, int nsoups, const BatchCycleParams &cp, hipStream_t s);
 hipError_t launch_batch_cycle_life(int W, int R, int nsoups, const BatchCycleParams &cp, hipStream_t s);

@@ -11,6 +11,7 @@ same SONAMEs as /opt/rocm's, so loading torch first makes libgolhip bind to torc
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 from pathlib import Path
@@ -67,7 +68,7 @@ EXPORTS = [
     "golhip_batch_track_period", "golhip_batch_periods", "golhip_batch_search",
     "golhip_batch_search_exact",
     "golhip_batch_set_topology", "golhip_batch_get_topology", "golhip_batch_set_soup_box", "golhip_batch_get_soup_box",
-    "golhip_batch_census",
+    "golhip_batch_census", "golhip_batch_search_census",
 ]
 
 
@@ -108,6 +109,24 @@ def cycle_start_floor(repeat_turn: int, period: int) -> int:
     return half - 1 if period <= half else 0
 
 
+def search_census_turn(repeat_turn: int, period: int, cycle_start: int) -> int:
+    """ash_turn of Batch.search_census for a soup with this record and cycle_start: the turn of the
+    board the exact pass holds when it stops.  -1 without a repeat; 0 when repeat_turn == period;
+    else, with lo = cycle_start_floor(repeat_turn, period), the pass compares board(t + period) with
+    board(t) from t = lo, notices the first equality (t = cycle_start) once per 32 compares and
+    leaves 33 compares into that block of 32 -- at turn lo + period + 32 * ((cycle_start - lo) // 32)
+    + 34 -- unless its last compare, at t = repeat_turn - period, comes first: then repeat_turn.
+    Always cycle_start <= ash_turn <= repeat_turn."""
+    if repeat_turn < 0:
+        return -1
+    s = int(repeat_turn) - int(period)
+    if s <= 0:
+        return 0
+    lo = cycle_start_floor(repeat_turn, period)
+    leave = 32 * ((int(cycle_start) - lo) // 32) + 33  # the compare behind which the pass leaves
+    return lo + int(period) + leave + 1 if leave < s - lo else int(repeat_turn)
+
+
 class Pattern(ctypes.Structure):
     """golhip_pattern_t: one pattern of Batch.census, h rows of w cells (1..32 each).  Bit c of alive[r]:
     cell (r, c) must be alive; bit c of care[r]: cell (r, c) is looked at (alive is a subset of care)."""
@@ -116,6 +135,9 @@ class Pattern(ctypes.Structure):
 
 
 CENSUS_MAX_PATTERNS = 256
+
+# what Batch.search_census returns; an output that was not asked for is None
+SearchCensus = collections.namedtuple("SearchCensus", "records cycle_start ash_turn counts residue ash")
 
 
 def pattern(cells) -> Pattern:
@@ -381,6 +403,10 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
         "golhip_batch_set_soup_box": ([H, i32, i32], i32),
         "golhip_batch_get_soup_box": ([H, ctypes.POINTER(i32), ctypes.POINTER(i32)], i32),
         "golhip_batch_census": ([H, ctypes.c_void_p, i32, ctypes.c_void_p, ctypes.c_void_p], i32),
+        "golhip_batch_search_census": ([H, i64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, i64,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i32, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p], i32),
         "golhip_launch_kind_counts": ([H, i32, i32, ctypes.POINTER(ctypes.c_int),
                                        ctypes.POINTER(ctypes.c_int)], i32),
     }
@@ -947,7 +973,7 @@ class Batch:
     Soups: search() runs seeds, not boards of the batch, each until it repeats; search_exact() adds
     every soup's cycle_start, the exact turn at which it enters its cycle.  census() says what the
     boards hold: per board, how often each pattern of a list matches and how many live cells no match
-    explains."""
+    explains.  search_census() is search_exact() with that census of each soup's ash, no boards kept."""
 
     def __init__(self, width: int, height: int, nboards: int, device: int = 0, *,
                  rule: str | tuple[int, int] | None = None, rules=None, topology: str | int = "torus",
@@ -1171,6 +1197,72 @@ class Batch:
                                                       vptr, out.ctypes.data, cycle_start.ctypes.data))
         return out, cycle_start
 
+    @staticmethod
+    def _pattern_table(patterns):
+        """(npat, the ctypes array of Patterns) of census()'s `patterns`; a bad array raises
+        GolHipError(ERR_ARG) naming its index."""
+        pats = []
+        for i, p in enumerate(patterns):
+            if isinstance(p, Pattern):
+                pats.append(p)
+                continue
+            try:
+                pats.append(pattern(p))
+            except GolHipError as e:
+                raise GolHipError(e.code, f"pattern {i}: " + str(e).split(": ", 2)[2])
+        return len(pats), (Pattern * max(len(pats), 1))(*pats)
+
+    def search_census(self, nsoups: int, patterns, *, seeds=None, seed0: int = 0, density_q32: int = DENSITY_HALF,
+                      max_turns: int, rules=None, counts: bool = True, residue: bool = True,
+                      ash: bool = False) -> SearchCensus:
+        """search_exact() plus the census of each soup's ash, in one call and without boards
+        (golhip_batch_search_census).  Returns SearchCensus(records, cycle_start, ash_turn, counts,
+        residue, ash): records and cycle_start are search_exact()'s, byte for byte; ash_turn (int64)
+        is the turn of the board that was censused, cycle_start <= ash_turn <= repeat_turn, a board on
+        the soup's cycle (0 and the seeded board when repeat_turn == period); counts (nsoups, npat)
+        uint32 and residue (nsoups,) uint32 are census()'s of that board on the batch's topology; ash
+        (nsoups, h, w) uint8 is the board itself, 0 / 1.  An output switched off (counts=False,
+        residue=False; ash is off by default) is None and its work is skipped; at least one of the
+        three must be on, and without patterns counts must be off.  A soup without a repeat within
+        max_turns has ash_turn -1, a counts row of zeros, a dead ash and residue = its record's
+        population.
+
+        The recipe that reproduces the censused board of a soup: a Batch of this size with the same
+        soup_box and topology (and the soup's rule), init_random(seeds=[seed]), step(ash_turn);
+        census() there gives the same row.  The board is not aligned to cycle_start's phase: an
+        oscillating ash is seen in the phase of turn ash_turn, so list oscillators in every phase
+        (common_objects() does).  ash_turn depends on the record and cycle_start only, and every
+        output on what a record depends on plus the patterns: not on nsoups, the position or which
+        outputs are on.
+
+        patterns, the errors of a bad pattern and their wording are census()'s; seeds, seed0,
+        density_q32, max_turns, rules and their errors are search()'s.  The batch's boards, turn,
+        rules, records and switches are left as they were."""
+        nsoups = int(nsoups)
+        npat, table = self._pattern_table(patterns)
+        sptr = bptr = vptr = None
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+            if seeds.shape != (max(nsoups, 0),):
+                raise GolHipError(ERR_ARG, f"seeds: shape {seeds.shape} for {nsoups} soups")
+            sptr = seeds.ctypes.data
+        if rules is not None:
+            pairs = self._pairs_of(rules, nsoups)
+            birth, survive = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+            bptr, vptr = birth.ctypes.data, survive.ctypes.data
+        n = max(nsoups, 0)
+        out = np.zeros(n, dtype=SOUP_DTYPE)
+        cycle_start = np.zeros(n, dtype=np.int64)
+        ash_turn = np.zeros(n, dtype=np.int64)
+        c = np.zeros((n, npat), dtype=np.uint32) if counts else None
+        r = np.zeros(n, dtype=np.uint32) if residue else None
+        a = np.zeros((n, self.height, self.width), dtype=np.uint8) if ash else None
+        self._check(self._L.golhip_batch_search_census(
+            self._h, nsoups, sptr, seed0, density_q32, max_turns, bptr, vptr, ctypes.addressof(table) if npat else None,
+            npat, out.ctypes.data, cycle_start.ctypes.data, ash_turn.ctypes.data, c.ctypes.data if counts else None,
+            r.ctypes.data if residue else None, a.ctypes.data if ash else None))
+        return SearchCensus(out, cycle_start, ash_turn, c, r, a)
+
     def census(self, patterns, *, counts: bool = True, residue: bool = True):
         """What the boards hold, by pattern matching on the device (golhip_batch_census).  patterns is
         a sequence of 2-D arrays (1 alive, 0 dead, -1 not looked at: pattern()) or Patterns, at most
@@ -1193,21 +1285,12 @@ class Batch:
         The workflow: (1) search() or search_exact(); (2) pick the seeds of interest; (3)
         Batch(w, h, len(seeds)), init_random(seeds=seeds), step(the largest stop_turn); (4)
         census(...).  An oscillating ash is seen in the phase of the turn the batch is at, which is
-        why common_objects() lists oscillators in every phase.
+        why common_objects() lists oscillators in every phase.  For the ash of the soups of a search
+        search_census() does all four in one call, without boards and without the extra generations.
 
         A bad pattern raises GolHipError(ERR_ARG) naming its index: an array before any device work,
         a Pattern (and a pattern larger than the board, or more than 256) from the library."""
-        pats = []
-        for i, p in enumerate(patterns):
-            if isinstance(p, Pattern):
-                pats.append(p)
-                continue
-            try:
-                pats.append(pattern(p))
-            except GolHipError as e:
-                raise GolHipError(e.code, f"pattern {i}: " + str(e).split(": ", 2)[2])
-        npat = len(pats)
-        table = (Pattern * max(npat, 1))(*pats)
+        npat, table = self._pattern_table(patterns)
         c = np.zeros((self.nboards, npat), dtype=np.uint32) if counts else None
         r = np.zeros(self.nboards, dtype=np.uint32) if residue else None
         self._check(self._L.golhip_batch_census(self._h, ctypes.addressof(table) if npat else None, npat,

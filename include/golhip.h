@@ -420,7 +420,9 @@ int golhip_edge_wait(golhip_t h, double *total_ms, int64_t *blocks);
  *     golhip_batch_search_exact (one chunk's seeds, rule pairs, records and cycle starts: 3.5 MiB)
  *     and the first golhip_batch_census (the pattern table: 66 KiB)
  *     allocates device memory: bytes, seeds, rules, counts, history and the census's results go
- *     through a transfer stage in chunks.
+ *     through a transfer stage in chunks.  One more call allocates: the first
+ *     golhip_batch_search_census (one chunk's ash boards, at most 64 MiB, and their turns, 512 KiB;
+ *     the search buffers and the pattern table too if no earlier call has).
  *   - A batch has ONE turn counter.  Any golhip_batch_load_bytes, even of part of the batch, and any
  *     golhip_batch_init_random set it to 0 and clear every settle and period record: a batch is filled, then run.
  *   - golhip_batch_init_random: board i is bit for bit what golhip_init_random(seed_i, density_q32)
@@ -655,6 +657,54 @@ typedef struct {
 int golhip_batch_census(golhip_batch_t b, const golhip_pattern_t *patterns, int npat,
                         uint32_t *counts  /* nboards * npat, or NULL */,
                         uint32_t *residue /* nboards, or NULL */);
+/* The soup search with a census of each soup's ash, no boards kept: golhip_batch_search_exact plus, per
+ * soup, the census of a board that lies on the soup's cycle.  The exact pass already holds such a
+ * board in registers when it has found cycle_start; it stores that board into a chunk-sized buffer
+ * and gol_batch_census runs over the buffer.  No second batch, no init_random, no stepping of every
+ * board to the slowest soup's turn.
+ *   - out is byte for byte what golhip_batch_search writes for the same arguments and cycle_start is
+ *     what golhip_batch_search_exact writes; both are required, as is ash_turn.
+ *   - The censused board of soup i is board_i(ash_turn[i]), the soup stepped ash_turn[i] generations
+ *     from its seed under the batch's topology and soup box and the soup's rule.  For a soup with a
+ *     repeat within max_turns, cycle_start <= ash_turn <= repeat_turn: the board is on the cycle and
+ *     no generation beyond repeat_turn has run.  ash_turn is 0, the board the seeded soup, when
+ *     repeat_turn == period (the soup is on its cycle and was noticed from the snapshot of turn 0:
+ *     an empty board, a still life).  ash_turn is a function of the soup's record and cycle_start
+ *     alone; it is NOT aligned to cycle_start's phase, so an oscillating ash is seen in the phase of
+ *     turn ash_turn: list an oscillator in every phase.
+ *   - The recipe that reproduces the censused board: a batch of the same size, topology and soup
+ *     box, golhip_batch_init_random with the soup's seed, golhip_batch_step(ash_turn) under the
+ *     soup's rule; golhip_batch_census of that board gives the same row.
+ *   - counts[i * npat + p] and residue[i] are golhip_batch_census's, word for word, of that board
+ *     under the batch's topology.  ash_cells[(i * height + y) * width + x] is its cell (x, y), 0 or 1.
+ *     Each of counts, residue and ash_cells may be NULL, not all three; npat == 0 is allowed when
+ *     counts is NULL, and residue is then the board's live cells.
+ *   - A soup without a repeat within max_turns has ash_turn -1, a counts row of zeros, ash_cells all
+ *     dead and residue = the record's population: the cells are alive and none is explained.
+ *   - Errors: golhip_batch_search's checks, then golhip_batch_census's checks of npat and the patterns,
+ *     in their words, all before any device work: GOLHIP_ERR_ARG, and the handle and every output
+ *     stay untouched.  Additionally GOLHIP_ERR_ARG: counts, residue and ash_cells all NULL; counts
+ *     with npat == 0; with nsoups > 0, out, cycle_start or ash_turn NULL.
+ *   - Side effects are golhip_batch_search's: the batch's boards, turn, rules, records, switches,
+ *     topology and box all stay.  The soup runs under the batch's uniform rule, or its own with birth
+ *     and survive, as in golhip_batch_search_exact.
+ *   - Independence.  Every output for soup i depends on what its record depends on and, for counts and
+ *     residue, on the patterns; not on nsoups, the soup's position, the chunking or
+ *     GOLHIP_STAGE_BYTES, nor on which of the optional outputs are asked for.
+ *   - Chunks, in stream order: the search launch, the chunk's ash buffer zeroed, gol_batch_cycle with
+ *     the buffer, the census over the buffer, the ash unpacked if ash_cells is set.  A chunk is
+ *     golhip_batch_search's, capped so that the ash buffer stays at or below 64 MiB: 65536 soups of
+ *     64 x 64, 2048 of 512 x 512.  The buffer is allocated by the first golhip_batch_search_census
+ *     and freed by golhip_batch_destroy. */
+int golhip_batch_search_census(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds /* nsoups, or NULL */,
+                               uint64_t seed0, uint32_t density_q32, int64_t max_turns,
+                               const uint32_t *birth /* nsoups, or NULL */, const uint32_t *survive,
+                               const golhip_pattern_t *patterns, int npat,
+                               golhip_soup_t *out /* nsoups */, int64_t *cycle_start /* nsoups */,
+                               int64_t *ash_turn /* nsoups */,
+                               uint32_t *counts  /* nsoups * npat, or NULL */,
+                               uint32_t *residue /* nsoups, or NULL */,
+                               uint8_t *ash_cells /* nsoups * height * width, or NULL */);
 
 #ifdef __cplusplus
 }

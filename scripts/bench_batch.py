@@ -69,6 +69,18 @@ store() of every board, alone, and with the brute force's time on the 64-board s
 boards added; (b) one census call, with the residue and without.  One search call on the same seeds
 and the 2000-turn step are timed once each, for scale.
 
+--search-census: Batch.search_census (the exact search with a census of each soup's ash, no boards kept)
+instead of the run above.  --batches soups (4096 and 65536 by default) of 64 x 64, seeds 0 .. B - 1 at
+density 1/2 under B3/S23, max_turns 16384 (--max-turns), the 33 arrays of common_objects().  Before
+anything is timed the records and cycle_start must be search_exact's, cycle_start <= ash_turn <=
+repeat_turn must hold, ash_turn must be search_census_turn's, and for 8 soups init_random(seed) +
+step(ash_turn) + census on a one-board batch must reproduce the row.  Timed, host clock around whole
+calls: (a) search_exact of this library alternated call by call with search_exact of --parent-lib (a
+build of the commit before this call existed), with the parent's own min and max as the run-to-run
+spread; (b) search_census beside search_exact; (c) the route it replaces, search_exact + init_random
++ step(the largest stop_turn) + census on a batch of B boards (--route-calls times: a call steps every
+board to the slowest soup's turn).  Also the ash totals per object.
+
 One JSON line on stdout; --out also writes it to a file.  There is no CPU fallback: without a GPU
 the script fails.
 """
@@ -375,6 +387,104 @@ def census_leg(a, res):
 CENSUS_TURNS = 2000
 
 
+def load_older_library(path):
+    """A libgolhip.so built from an earlier commit: it lacks the newest exports, which
+    golhip.load_library insists on, so what it has is bound with the current signatures."""
+    import ctypes
+
+    old, cur = ctypes.CDLL(str(path)), golhip.load_library()
+    for name in golhip.EXPORTS:
+        if hasattr(old, name):
+            getattr(old, name).argtypes = getattr(cur, name).argtypes
+            getattr(old, name).restype = getattr(cur, name).restype
+    return old
+
+
+def search_census_leg(a, res):
+    """Batch.search_census beside search_exact (this library's and, alternated, the parent build's) and
+    beside the four-call route it replaces, in this process."""
+    res["bench"] = "batch_search_census"
+    max_turns = a.max_turns or 16384
+    res["max_turns"] = max_turns
+    objs = golhip.common_objects()
+    pats = [p for v in objs.values() for p in v]
+    names = [k for k, v in objs.items() for _ in v]
+    res["patterns"] = len(pats)
+    parent = load_older_library(a.parent_lib) if a.parent_lib else None
+    res["parent_version"] = parent.golhip_version() if parent else None
+    for B in ([int(v) for v in a.batches.split(",")] if a.batches else [4096, 65536]):
+        seeds = np.arange(B, dtype=np.uint64)
+        with golhip.Batch(64, 64, 1) as b:
+            got = b.search_census(B, pats, seeds=seeds, max_turns=max_turns)
+            rec, start = b.search_exact(B, seeds=seeds, max_turns=max_turns)
+            assert got.records.tobytes() == rec.tobytes() and np.array_equal(got.cycle_start, start), B
+            found = rec["repeat_turn"] > 0
+            assert ((start <= got.ash_turn) & (got.ash_turn <= rec["repeat_turn"]))[found].all(), B
+            assert (got.ash_turn[~found] == -1).all() and np.array_equal(got.residue[~found], rec["population"][~found])
+            model = [golhip.search_census_turn(int(r), int(p), int(s))
+                     for r, p, s in zip(rec["repeat_turn"][:4096], rec["period"][:4096], start[:4096])]
+            assert got.ash_turn[:4096].tolist() == model, B
+            for i in np.nonzero(found)[0][:8]:  # the recipe
+                with golhip.Batch(64, 64, 1) as look:
+                    look.init_random(seeds=seeds[i:i + 1])
+                    look.step(int(got.ash_turn[i]))
+                    c1, r1 = look.census(pats)
+                assert np.array_equal(c1[0], got.counts[i]) and r1[0] == got.residue[i], (B, i)
+
+            def exact():
+                return b.search_exact(B, seeds=seeds, max_turns=max_turns)
+
+            def census():
+                return b.search_census(B, pats, seeds=seeds, max_turns=max_turns)
+
+            tree_ts, parent_ts = [], []
+            if parent:
+                with golhip.Batch(64, 64, 1, lib=parent) as pb:
+                    def parent_exact():
+                        return pb.search_exact(B, seeds=seeds, max_turns=max_turns)
+
+                    prec, pstart = parent_exact()
+                    assert prec.tobytes() == rec.tobytes() and np.array_equal(pstart, start), B
+                    for fn in (parent_exact, exact, parent_exact, exact):  # 2 warm calls each
+                        fn()
+                    for _ in range(a.calls):
+                        for fn, ts in ((parent_exact, parent_ts), (exact, tree_ts)):
+                            t0 = time.perf_counter()
+                            fn()
+                            ts.append(time.perf_counter() - t0)
+                exact_med, exact_min = statistics.median(tree_ts), min(tree_ts)
+            else:
+                exact_med, exact_min = median_s(exact, 2, a.calls)
+            census_med, census_min = median_s(census, 2, a.calls)
+        lib = parent if parent else None
+        with golhip.Batch(64, 64, B, lib=lib) as rb:
+            def route():
+                r, _ = rb.search_exact(B, seeds=seeds, max_turns=max_turns)
+                rb.init_random(seeds=seeds)
+                rb.step(int(r["stop_turn"].max()))
+                return rb.census(pats)
+
+            route_med, route_min = median_s(route, 2, a.route_calls)
+        totals = {k: int(sum(int(got.counts[:, i].sum()) for i, n in enumerate(names) if n == k)) for k in objs}
+        row = {"width": 64, "height": 64, "soups": B, "totals": totals,
+               "soups_with_a_repeat": int(found.sum()), "soups_with_residue_0": int((got.residue == 0).sum()),
+               "mean_repeat_turn": round(float(rec["repeat_turn"][found].mean()), 1),
+               "mean_ash_turn": round(float(got.ash_turn[found].mean()), 1), "max_stop_turn": int(rec["stop_turn"].max()),
+               "exact_ms_median": round(exact_med * 1e3, 3), "exact_ms_min": round(exact_min * 1e3, 3),
+               "exact_ms_max": round(max(tree_ts) * 1e3, 3) if tree_ts else None,
+               "parent_exact_ms_median": round(statistics.median(parent_ts) * 1e3, 3) if parent_ts else None,
+               "parent_exact_ms_min": round(min(parent_ts) * 1e3, 3) if parent_ts else None,
+               "parent_exact_ms_max": round(max(parent_ts) * 1e3, 3) if parent_ts else None,
+               "exact_over_parent_exact": round(exact_med / statistics.median(parent_ts), 4) if parent_ts else None,
+               "search_census_ms_median": round(census_med * 1e3, 3), "search_census_ms_min": round(census_min * 1e3, 3),
+               "search_census_over_exact": round(census_med / exact_med, 4),
+               "route_calls": a.route_calls, "route_library": "parent" if parent else "this",
+               "route_ms_median": round(route_med * 1e3, 1), "route_ms_min": round(route_min * 1e3, 1),
+               "route_over_search_census": round(route_med / census_med, 2)}
+        res["shapes"].append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=7)
@@ -393,9 +503,24 @@ def main():
     ap.add_argument("--max-turns", type=int, help="--plane, --exact: instead of the cases' max_turns")
     ap.add_argument("--exact", action="store_true", help="search_exact beside search (see above)")
     ap.add_argument("--census", action="store_true", help="Batch.census beside store() + numpy (see above)")
+    ap.add_argument("--search-census", action="store_true",
+                    help="Batch.search_census beside search_exact and the route it replaces (see above)")
+    ap.add_argument("--parent-lib", type=Path, help="--search-census: a libgolhip.so built from the parent commit")
+    ap.add_argument("--route-calls", type=int, default=3, help="--search-census: timed calls of the replaced route")
     a = ap.parse_args()
     assert a.calls >= 7
     assert a.rule or not a.per_board_rules, "--per-board-rules needs --rule"
+    if a.search_census:
+        assert not (a.census or a.exact or a.plane or a.search or a.period or a.rule), "--search-census replaces the other legs"
+        res = {"bench": "batch_search_census", "version": golhip.load_library().golhip_version(), "calls": a.calls,
+               "shapes": []}
+        search_census_leg(a, res)
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            a.out.parent.mkdir(parents=True, exist_ok=True)
+            a.out.write_text(line + "\n")
+        return
     if a.census:
         assert not (a.exact or a.plane or a.search or a.period or a.rule), "--census replaces the other legs"
         res = {"bench": "batch_census", "version": golhip.load_library().golhip_version(), "turns": None,
