@@ -43,6 +43,11 @@
 //
 // The census (golhip_batch_census) runs gol_batch_census (batch_census.hpp) over the boards as they are:
 // it reads the boards and the topology and writes nothing the handle owns.
+//
+// The objects (golhip_batch_objects) run gol_batch_objects (batch_objects.hpp) over the boards in the same
+// way, and golhip_batch_search_objects runs it over a chunk's ash where the search census runs the census.
+// Their counts and records come back through the search census's stage and, the records, through
+// pinned host memory, both allocated by the first call that needs them: objects_boards.
 #include <algorithm>
 #include <cstdarg>
 #include <cstddef>
@@ -86,6 +91,8 @@ struct golhip_batch {
     int64_t search_stage_bytes = 0;
     int64_t stage_limit = 0;              // GOLHIP_STAGE_BYTES at create, 0 without: it caps that stage too
     golhip::CensusPattern *census_pat = nullptr;  // golhip_batch_census: the pattern table of a call
+    uint8_t *objects_host = nullptr;      // golhip_batch_objects / _search_objects: a chunk's records on the
+    int64_t objects_host_bytes = 0;       // host (pinned), from which each board's written ones are copied
     int topology = GOLHIP_TOPOLOGY_TORUS;
     int box_w = 0, box_h = 0;  // the soup box of init_random and search; 0, 0: the whole board
     std::string err;
@@ -136,6 +143,7 @@ void batch_free(golhip_batch_t b) {
     if (b->search_ash_turn) (void)hipFree(b->search_ash_turn);
     if (b->search_stage) (void)hipFree(b->search_stage);
     if (b->census_pat) (void)hipFree(b->census_pat);
+    if (b->objects_host) (void)hipHostFree(b->objects_host);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     b->boards = b->prev = b->rules = b->snap = nullptr;
     b->last_diff = nullptr;
@@ -150,6 +158,8 @@ void batch_free(golhip_batch_t b) {
     b->search_stage = nullptr;
     b->search_stage_bytes = 0;
     b->census_pat = nullptr;
+    b->objects_host = nullptr;
+    b->objects_host_bytes = 0;
     b->stream = nullptr;
 }
 
@@ -623,15 +633,45 @@ struct SearchCensus {
     uint32_t *counts, *residue;
     uint8_t *ash_cells;
 };
+// golhip_batch_search_objects (so set) is the same call with gol_batch_objects over the ash buffer in the
+// census's place.
+struct SearchObjects {
+    int max_objects, reach;
+    int64_t *ash_turn;
+    int32_t *nobjects;
+    golhip_object_t *objects;
+};
 constexpr int64_t kAshBytes = (int64_t)64 << 20;  // the ash buffer of a chunk, at most
+constexpr int64_t kObjectsStageFloor = 4 + (int64_t)sizeof(golhip_object_t);  // a count and one record
+static int objects_check(golhip_batch_t b, int max_objects, int reach);
+static int objects_boards(golhip_batch_t b, const uint32_t *base, int64_t nboards, int max_objects, int reach,
+                          int32_t *nobjects, golhip_object_t *objects);
+
+// The stage of golhip_batch_search_census and of the objects calls: `need` bytes, at most 64 MiB; the test
+// hook shrinks it as it shrinks the batch's, never below floor_bytes; it only grows.
+static int reserve_search_stage(golhip_batch_t b, int64_t need, int64_t floor_bytes) {
+    need = std::min(need, kAshBytes);
+    if (b->stage_limit) need = std::min(need, std::max<int64_t>(b->stage_limit, floor_bytes));
+    if (need > b->search_stage_bytes) {
+        if (b->search_stage) BHIPCHK(b, hipFree(b->search_stage));
+        b->search_stage = nullptr;
+        b->search_stage_bytes = 0;
+        BHIPCHK(b, hipMalloc(&b->search_stage, (size_t)need));
+        b->search_stage_bytes = need;
+    }
+    return GOLHIP_OK;
+}
 static int census_check(golhip_batch_t b, const golhip_pattern_t *patterns, int npat);
 static int census_boards(golhip_batch_t b, const uint32_t *base, int64_t nboards, int npat, uint32_t *counts,
                          uint32_t *residue, uint32_t *stage, int64_t cap);
 
 static int search_run(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds, uint64_t seed0, uint32_t density_q32,
                       int64_t max_turns, const uint32_t *birth, const uint32_t *survive, golhip_soup_t *out,
-                      int64_t *cycle_start, bool exact, const SearchCensus *sc = nullptr) {
+                      int64_t *cycle_start, bool exact, const SearchCensus *sc = nullptr,
+                      const SearchObjects *so = nullptr) {
     if (!b) return GOLHIP_ERR_ARG;
+    const bool ashed = sc || so;
+    int64_t *const ash_turn = sc ? sc->ash_turn : so ? so->ash_turn : nullptr;
     if (b->width % 64 != 0)
         return bfail(b, GOLHIP_ERR_ARG, "search needs width %% 64 == 0, as init_random (width %lld)", (long long)b->width);
     if (max_turns < 1 || max_turns > kSearchMaxTurns)
@@ -658,10 +698,15 @@ static int search_run(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds, u
         const int rc = census_check(b, sc->patterns, sc->npat);
         if (rc) return rc;
     }
+    if (so) {  // the checks of golhip_batch_objects, in its words
+        const int rc = objects_check(b, so->max_objects, so->reach);
+        if (rc) return rc;
+    }
     if (nsoups == 0) return GOLHIP_OK;
     if (!out) return bfail(b, GOLHIP_ERR_ARG, "out is null");
     if (exact && !cycle_start) return bfail(b, GOLHIP_ERR_ARG, "cycle_start is null");
-    if (sc && !sc->ash_turn) return bfail(b, GOLHIP_ERR_ARG, "ash_turn is null");
+    if (ashed && !ash_turn) return bfail(b, GOLHIP_ERR_ARG, "ash_turn is null");
+    if (so && !so->nobjects) return bfail(b, GOLHIP_ERR_ARG, "objects nobjects is null");
     static_assert(sizeof(golhip_soup_t) == 32 && sizeof(SoupRecord) == 32, "a soup's record is 32 bytes");
     static_assert(offsetof(golhip_soup_t, repeat_turn) == offsetof(SoupRecord, repeat_turn) &&
                       offsetof(golhip_soup_t, period) == offsetof(SoupRecord, period) &&
@@ -677,7 +722,7 @@ static int search_run(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds, u
     // a chunk: at most kSearchChunk soups and at most 2^44 cell updates if no soup repeats, at least 1
     int64_t chunk = std::max<int64_t>(
         1, std::min<int64_t>(kSearchChunk, kSearchChunkUpdates / (b->width * b->height * max_turns)));
-    if (sc) {  // and no more soups than the ash buffer holds boards: 64 MiB, at least one board
+    if (ashed) {  // and no more soups than the ash buffer holds boards: 64 MiB, at least one board
         const int64_t board_bytes = (int64_t)sizeof(uint32_t) * b->board_words;
         const int64_t ash_boards = std::max<int64_t>(1, std::min<int64_t>(kSearchChunk, kAshBytes / board_bytes));
         if (!b->search_ash) BHIPCHK(b, hipMalloc(&b->search_ash, (size_t)(ash_boards * board_bytes)));
@@ -687,19 +732,14 @@ static int search_run(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds, u
         // by nboards and a search runs on a batch of one board: a chunk's counts and residues, and
         // its cells if they are asked for, at most 64 MiB; it only grows.
         const int64_t most = std::min(chunk, nsoups);
-        int64_t need = 4 * most * ((sc->counts ? sc->npat : 0) + 1);
-        if (sc->ash_cells) need = std::max(need, most * b->width * b->height);
-        need = std::min(need, kAshBytes);
-        // the test hook shrinks this stage as it shrinks the batch's: never below a byte row or a uint32
-        if (b->stage_limit) need = std::min(need, std::max<int64_t>(b->stage_limit, std::max<int64_t>(b->width, 4)));
-        if (need > b->search_stage_bytes) {
-            if (b->search_stage) BHIPCHK(b, hipFree(b->search_stage));
-            b->search_stage = nullptr;
-            b->search_stage_bytes = 0;
-            BHIPCHK(b, hipMalloc(&b->search_stage, (size_t)need));
-            b->search_stage_bytes = need;
+        if (sc) {
+            int64_t need = 4 * most * ((sc->counts ? sc->npat : 0) + 1);
+            if (sc->ash_cells) need = std::max(need, most * b->width * b->height);
+            // the test hook shrinks this stage as it shrinks the batch's: never below a byte row or a uint32
+            const int rc = reserve_search_stage(b, need, std::max<int64_t>(b->width, 4));
+            if (rc) return rc;
         }
-        if (sc->npat > 0 && (sc->counts || sc->residue)) {
+        if (sc && sc->npat > 0 && (sc->counts || sc->residue)) {
             if (!b->census_pat)
                 BHIPCHK(b, hipMalloc(&b->census_pat, sizeof(CensusPattern) * (size_t)kCensusMaxPatterns));
             BHIPCHK(b, hipMemcpyAsync(b->census_pat, sc->patterns, sizeof(CensusPattern) * (size_t)sc->npat,
@@ -744,7 +784,7 @@ static int search_run(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds, u
                                   b->stream));
         if (exact) {  // the second pass reads the chunk's records on the device (stream order)
             BatchCycleParams cp{{sp, soup_box(b), b->topology == GOLHIP_TOPOLOGY_PLANE ? 1 : 0}, b->search_cycle};
-            if (sc) {  // a soup without a repeat writes no row: its ash is the empty board
+            if (ashed) {  // a soup without a repeat writes no row: its ash is the empty board
                 BHIPCHK(b, hipMemsetAsync(b->search_ash, 0, sizeof(uint32_t) * (size_t)(n * b->board_words), b->stream));
                 cp.ash = b->search_ash;
                 cp.ash_turn = b->search_ash_turn;
@@ -753,8 +793,15 @@ static int search_run(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds, u
             BHIPCHK(b, hipMemcpyAsync(cycle_start + i, b->search_cycle, sizeof(int64_t) * (size_t)n,
                                       hipMemcpyDeviceToHost, b->stream));
         }
+        if (so) {  // the empty ash of a soup without a repeat has no cluster: nobjects 0
+            BHIPCHK(b, hipMemcpyAsync(ash_turn + i, b->search_ash_turn, sizeof(int64_t) * (size_t)n,
+                                      hipMemcpyDeviceToHost, b->stream));
+            const int rc = objects_boards(b, b->search_ash, n, so->max_objects, so->reach, so->nobjects + i,
+                                          so->objects ? so->objects + i * so->max_objects : nullptr);
+            if (rc) return rc;
+        }
         if (sc) {
-            BHIPCHK(b, hipMemcpyAsync(sc->ash_turn + i, b->search_ash_turn, sizeof(int64_t) * (size_t)n,
+            BHIPCHK(b, hipMemcpyAsync(ash_turn + i, b->search_ash_turn, sizeof(int64_t) * (size_t)n,
                                       hipMemcpyDeviceToHost, b->stream));
             uint32_t *res = sc->residue ? sc->residue + i : nullptr;
             if (sc->npat > 0 && (sc->counts || res)) {
@@ -918,6 +965,102 @@ int golhip_batch_census(golhip_batch_t b, const golhip_pattern_t *patterns, int 
     // the batch's stage: >= nboards >= 1 words
     return census_boards(b, b->boards, b->nboards, npat, counts, residue, reinterpret_cast<uint32_t *>(b->stage),
                          b->stage_bytes / 4);
+}
+
+// The checks of the objects calls; the text names the argument and its range.
+static int objects_check(golhip_batch_t b, int max_objects, int reach) {
+    if (max_objects < 1 || max_objects > kObjectsMax)
+        return bfail(b, GOLHIP_ERR_ARG, "objects max_objects %d: 1 to %d", max_objects, kObjectsMax);
+    if (reach != 1 && reach != 2) return bfail(b, GOLHIP_ERR_ARG, "objects reach %d: 1 or 2", reach);
+    return GOLHIP_OK;
+}
+
+// The clusters of `nboards` boards of the batch layout at `base` -- the batch's own, or one chunk of
+// golhip_batch_search_objects's ash.  nobjects (nboards) and objects (nboards x max_objects, or null) are
+// host memory.  The results come back through the search stage, at most 64 MiB and what
+// GOLHIP_STAGE_BYTES allows: where it holds a board's count and its max_objects records, chunks of
+// boards, one launch each; a smaller stage takes one board at a time and its records in windows, one
+// launch per window, as far as the board has clusters.  A launch writes only the records that exist,
+// so a chunk's records go to pinned host memory first and each board's written ones from there.
+static int objects_boards(golhip_batch_t b, const uint32_t *base, int64_t nboards, int max_objects, int reach,
+                          int32_t *nobjects, golhip_object_t *objects) {
+    static_assert(sizeof(golhip_object_t) == 32 && sizeof(ObjectRecord) == 32 &&
+                      offsetof(golhip_object_t, population) == offsetof(ObjectRecord, population) &&
+                      offsetof(golhip_object_t, flags) == offsetof(ObjectRecord, flags) &&
+                      offsetof(golhip_object_t, hash) == offsetof(ObjectRecord, hash),
+                  "the kernel's record is golhip_object_t");
+    constexpr int64_t kRec = (int64_t)sizeof(golhip_object_t);
+    const int64_t per_board = 4 + (objects ? kRec * max_objects : 0);
+    int rc = reserve_search_stage(b, per_board * std::min<int64_t>(nboards, kSearchChunk), kObjectsStageFloor);
+    if (rc) return rc;
+    const int64_t cap = b->search_stage_bytes;
+    const int64_t window = !objects || cap >= per_board ? max_objects : (cap - 4) / kRec;
+    const int64_t chunk = !objects ? std::min<int64_t>(kSearchChunk, cap / 4)
+                                   : std::max<int64_t>(1, std::min<int64_t>(kSearchChunk, cap / (4 + kRec * window)));
+    if (objects && chunk * window * kRec > b->objects_host_bytes) {
+        if (b->objects_host) BHIPCHK(b, hipHostFree(b->objects_host));
+        b->objects_host = nullptr;
+        b->objects_host_bytes = 0;
+        BHIPCHK(b, hipHostMalloc(reinterpret_cast<void **>(&b->objects_host), (size_t)(chunk * window * kRec)));
+        b->objects_host_bytes = chunk * window * kRec;
+    }
+    BatchObjectsParams op{};
+    op.board_pitch = b->board_words;
+    op.wd = b->wd;
+    op.width = (int32_t)b->width;
+    op.height = (int32_t)b->height;
+    op.plane = b->topology == GOLHIP_TOPOLOGY_PLANE ? 1 : 0;
+    op.reach = reach;
+    op.max_objects = max_objects;
+    op.window = (int32_t)window;
+    for (int64_t i = 0; i < nboards; i += chunk) {
+        const int64_t n = std::min<int64_t>(chunk, nboards - i);
+        // the records first (8-byte aligned: the stage is), the counts behind them
+        op.boards = base + i * b->board_words;
+        op.objects = objects ? reinterpret_cast<ObjectRecord *>(b->search_stage) : nullptr;
+        op.nobjects = reinterpret_cast<int32_t *>(b->search_stage + (objects ? n * window * kRec : 0));
+        int64_t stored = 0;  // the records of the chunk's fullest board, cut at the cap
+        for (int64_t first = 0; first == 0 || first < stored; first += window) {
+            op.first = (int32_t)first;
+            BHIPCHK(b, launch_batch_objects((int)n, op, b->stream));  // a missing kernel is an error
+            if (first == 0) {
+                BHIPCHK(b, hipMemcpyAsync(nobjects + i, op.nobjects, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost,
+                                          b->stream));
+                BHIPCHK(b, hipStreamSynchronize(b->stream));
+                for (int64_t j = 0; j < n; ++j) stored = std::max<int64_t>(stored, std::min<int64_t>(nobjects[i + j], max_objects));
+            }
+            if (!objects || stored == 0) break;
+            const int64_t cols = std::min(window, stored - first);  // per board, the widest row of this window
+            BHIPCHK(b, hipMemcpy2DAsync(b->objects_host, (size_t)(cols * kRec), op.objects, (size_t)(window * kRec),
+                                        (size_t)(cols * kRec), (size_t)n, hipMemcpyDeviceToHost, b->stream));
+            BHIPCHK(b, hipStreamSynchronize(b->stream));  // the next launch rewrites the stage
+            for (int64_t j = 0; j < n; ++j) {
+                const int64_t m = std::min<int64_t>(std::min<int64_t>(nobjects[i + j], max_objects) - first, cols);
+                if (m > 0)
+                    std::memcpy(objects + (i + j) * max_objects + first, b->objects_host + j * cols * kRec, (size_t)(m * kRec));
+            }
+        }
+    }
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    return GOLHIP_OK;
+}
+
+int golhip_batch_objects(golhip_batch_t b, int max_objects, int reach, int32_t *nobjects, golhip_object_t *objects) {
+    if (!b) return GOLHIP_ERR_ARG;
+    const int rc = objects_check(b, max_objects, reach);
+    if (rc) return rc;
+    if (!nobjects) return bfail(b, GOLHIP_ERR_ARG, "objects nobjects is null");
+    BHIPCHK(b, hipSetDevice(b->device));
+    return objects_boards(b, b->boards, b->nboards, max_objects, reach, nobjects, objects);
+}
+
+int golhip_batch_search_objects(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds, uint64_t seed0,
+                                uint32_t density_q32, int64_t max_turns, const uint32_t *birth, const uint32_t *survive,
+                                int max_objects, int reach, golhip_soup_t *out, int64_t *cycle_start, int64_t *ash_turn,
+                                int32_t *nobjects, golhip_object_t *objects) {
+    const SearchObjects so{max_objects, reach, ash_turn, nobjects, objects};
+    return search_run(b, nsoups, seeds, seed0, density_q32, max_turns, birth, survive, out, cycle_start, true, nullptr,
+                      &so);
 }
 
 int golhip_batch_set_topology(golhip_batch_t b, int topology) {

@@ -39,7 +39,7 @@
 
 namespace golhip {
 
-constexpr int kVersion = 112;  // 112: golhip_batch_search_census; 111: golhip_batch_census; 110: golhip_batch_search_exact; 109: golhip_batch_set_topology / _set_soup_box; 108: golhip_batch_search; 107: golhip_batch_track_period / _periods; 106: golhip_batch_set_rule / _set_rules / _kernel (105: golhip_batch_*; 104: golhip_store_rect / _load_rect / _view_counts / _view)
+constexpr int kVersion = 113;  // 113: golhip_batch_objects / _search_objects; 112: golhip_batch_search_census; 111: golhip_batch_census; 110: golhip_batch_search_exact; 109: golhip_batch_set_topology / _set_soup_box; 108: golhip_batch_search; 107: golhip_batch_track_period / _periods; 106: golhip_batch_set_rule / _set_rules / _kernel (105: golhip_batch_*; 104: golhip_store_rect / _load_rect / _view_counts / _view)
 // Generations of per-turn counts finalized per launch (golhip_set_count_window changes it; at
 // least the graph length kGraphGens: tests shrink it to exercise flushes).
 constexpr int kCountWindowDefault = 4096;

@@ -470,6 +470,33 @@ struct BatchCensusParams {
     uint32_t *counts, *residue;
 };
 hipError_t launch_batch_census(int nboards, const BatchCensusParams &cp, hipStream_t s);
+// The objects (gol_batch_objects, batch_objects.hpp; ONE kernel in one translation unit,
+// batch_objects.hip, with run-time width, height, topology, reach and cap): board i of the launch is
+// boards + i * board_pitch in the batch layout, nboards <= 65536.  nobjects[i] = the clusters of
+// board i, all of them; objects, if set, holds `window` records per board, and cluster j of board i
+// (include/golhip.h: golhip_batch_objects has the definitions and the order) is stored at
+// objects[i * window + j - first] when first <= j < min(first + window, max_objects).  All pointers
+// are device memory.
+struct ObjectRecord {  // golhip_object_t (include/golhip.h)
+    int32_t x, y, w, h;
+    int32_t population;
+    uint32_t flags;
+    uint64_t hash;
+};
+constexpr int kObjectsMax = 4096;
+constexpr uint32_t kObjectWindsX = 1u, kObjectWindsY = 2u, kObjectAtBorder = 4u;
+struct BatchObjectsParams {
+    const uint32_t *boards;
+    int64_t board_pitch;
+    int32_t wd, width, height;  // words per torus row, cells per board row, rows
+    int32_t plane;
+    int32_t reach;        // 1 or 2
+    int32_t max_objects;  // 1 .. kObjectsMax
+    int32_t first, window;
+    int32_t *nobjects;
+    ObjectRecord *objects;  // or null: the counts alone
+};
+hipError_t launch_batch_objects(int nboards, const BatchObjectsParams &op, hipStream_t s);
 // Clears every cell outside the box in boards of the batch layout (after launch_batch_init_random).
 hipError_t launch_batch_clip_box(uint32_t *boards, int64_t board_pitch, int64_t nboards, int64_t rows, int64_t width,
                                  int32_t wd, const SoupBox &box, hipStream_t s);

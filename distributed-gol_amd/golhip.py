@@ -69,6 +69,7 @@ EXPORTS = [
     "golhip_batch_search_exact",
     "golhip_batch_set_topology", "golhip_batch_get_topology", "golhip_batch_set_soup_box", "golhip_batch_get_soup_box",
     "golhip_batch_census", "golhip_batch_search_census",
+    "golhip_batch_objects", "golhip_batch_search_objects",
 ]
 
 
@@ -138,6 +139,66 @@ CENSUS_MAX_PATTERNS = 256
 
 # what Batch.search_census returns; an output that was not asked for is None
 SearchCensus = collections.namedtuple("SearchCensus", "records cycle_start ash_turn counts residue ash")
+
+
+# golhip_object_t: one cluster of Batch.objects.  flags: OBJECT_WINDS_X | OBJECT_WINDS_Y | OBJECT_AT_BORDER
+OBJECT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"), ("population", "<i4"),
+                         ("flags", "<u4"), ("hash", "<u8")])
+OBJECT_WINDS_X, OBJECT_WINDS_Y, OBJECT_AT_BORDER = 1, 2, 4
+OBJECTS_MAX = 4096
+
+# what Batch.search_objects returns
+SearchObjects = collections.namedtuple("SearchObjects", "records cycle_start ash_turn nobjects objects")
+
+_M64 = (1 << 64) - 1
+
+
+def _mix64(v: int) -> int:
+    """mix(v) of include/golhip.h: the splitmix64 finaliser."""
+    z = (v + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def object_hash(cells) -> int:
+    """The hash Batch.objects gives a cluster of this shape that does not wind: all live (nonzero)
+    cells of the 2-D array taken as ONE object, whatever their distances, in the box of their
+    extent.  The same for every translation, rotation and reflection of the shape (include/golhip.h
+    has the definition: the smallest over the eight orientations of the sum of mix(v << 16 | u) over
+    the cells XOR mix(1 << 32 | oh << 16 | ow)).  Pure Python, no library call.  GolHipError(ERR_ARG)
+    for an array that is not 2-D or has no live cell."""
+    a = np.asarray(cells)
+    if a.ndim != 2:
+        raise GolHipError(ERR_ARG, f"object_hash: a 2-D array, not {a.ndim}-D")
+    ys, xs = np.nonzero(a)
+    if len(ys) == 0:
+        raise GolHipError(ERR_ARG, "object_hash: no live cell")
+    x0, y0 = int(xs.min()), int(ys.min())
+    w, h = int(xs.max()) - x0 + 1, int(ys.max()) - y0 + 1
+    place = [(int(x) - x0, int(y) - y0) for x, y in zip(xs, ys)]
+    best = None
+    for k in range(8):
+        total = 0
+        for dx, dy in place:
+            fx, fy = (w - 1 - dx if k & 1 else dx), (h - 1 - dy if k & 2 else dy)
+            u, v = (fx, fy) if k < 4 else (fy, fx)
+            total += _mix64(v << 16 | u)
+        ow, oh = (w, h) if k < 4 else (h, w)
+        hk = (total & _M64) ^ _mix64(1 << 32 | oh << 16 | ow)
+        best = hk if best is None or hk < best else best
+    return best
+
+
+def common_object_hashes() -> dict[int, str]:
+    """{hash: name} of every phase of the nine objects of common_objects(): the keys under which
+    Batch.objects reports them.  Orientations need no entries of their own, the hash does not change
+    under them."""
+    out = {}
+    for name, phases in _COMMON_OBJECTS.items():
+        for text in phases:
+            out[object_hash(np.array([[ch == "O" for ch in row] for row in text.split("/")], dtype=np.int8))] = name
+    return out
 
 
 def pattern(cells) -> Pattern:
@@ -407,6 +468,10 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i32, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p], i32),
+        "golhip_batch_objects": ([H, i32, i32, ctypes.c_void_p, ctypes.c_void_p], i32),
+        "golhip_batch_search_objects": ([H, i64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, i64,
+                                         ctypes.c_void_p, ctypes.c_void_p, i32, i32, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], i32),
         "golhip_launch_kind_counts": ([H, i32, i32, ctypes.POINTER(ctypes.c_int),
                                        ctypes.POINTER(ctypes.c_int)], i32),
     }
@@ -1297,6 +1362,66 @@ class Batch:
                                                 c.ctypes.data if counts else None,
                                                 r.ctypes.data if residue else None))
         return c, r
+
+    def objects(self, max_objects: int = 64, reach: int = 2):
+        """Every cluster of live cells of every board, found and hashed on the device
+        (golhip_batch_objects).  Returns (nobjects, objects): nobjects (nboards,) int32 is each board's
+        number of clusters, all of them; objects (nboards, max_objects) of OBJECT_DTYPE holds the first
+        min(nobjects[i], max_objects) of board i in row-major order of their first cell, the rest
+        zeros.  max_objects is 1..4096, reach 1 or 2.
+
+        Two live cells are linked when their Chebyshev distance is at most reach (mod width and mod
+        height on a torus, in the rectangle on a plane); a cluster is a connected component.  reach
+        1 gives 8-connected islands, reach 2 (the default) joins cells whose neighbourhoods share a
+        cell, so two clusters cannot influence each other in the next generation.  x, y, w, h are the
+        extent (on a torus it starts behind the cluster's run of empty columns; a cluster without
+        one winds: x 0, w width, OBJECT_WINDS_X), population the cells, flags OBJECT_WINDS_X / _WINDS_Y /
+        _AT_BORDER (a plane only: a cell in the outermost row or column).  hash is the same for every
+        translation, rotation and reflection of a cluster that does not wind: object_hash(array) is
+        the key of a known object, common_object_hashes() names the commonest.  The tally of a batch:
+        np.unique(objects["hash"][np.arange(max_objects) < nobjects[:, None]], return_counts=True).
+
+        The result for a board depends on that board, the topology and reach only; max_objects only
+        cuts the list.  Nothing else moves: the boards, the turn, the rules, the records and the
+        switches stay."""
+        n = np.zeros(self.nboards, dtype=np.int32)
+        o = np.zeros((self.nboards, max(int(max_objects), 0)), dtype=OBJECT_DTYPE)
+        self._check(self._L.golhip_batch_objects(self._h, int(max_objects), int(reach), n.ctypes.data,
+                                                 o.ctypes.data if o.size else None))
+        return n, o
+
+    def search_objects(self, nsoups: int, *, max_objects: int = 64, reach: int = 2, seeds=None, seed0: int = 0,
+                       density_q32: int = DENSITY_HALF, max_turns: int, rules=None) -> SearchObjects:
+        """search_census() with the objects of each soup's ash in the census's place
+        (golhip_batch_search_objects).  Returns SearchObjects(records, cycle_start, ash_turn, nobjects,
+        objects): the first three are search_census()'s, byte for byte; nobjects (nsoups,) int32 and
+        objects (nsoups, max_objects) of OBJECT_DTYPE are objects()'s of the board the recipe of
+        search_census() reproduces: init_random(seeds=[seed]), step(ash_turn).  A soup without a repeat
+        within max_turns has ash_turn -1 and nobjects 0.  seeds, seed0, density_q32, max_turns, rules
+        and their errors are search()'s, max_objects and reach objects()'s.  The batch's boards, turn,
+        rules, records and switches are left as they were."""
+        nsoups = int(nsoups)
+        sptr = bptr = vptr = None
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+            if seeds.shape != (max(nsoups, 0),):
+                raise GolHipError(ERR_ARG, f"seeds: shape {seeds.shape} for {nsoups} soups")
+            sptr = seeds.ctypes.data
+        if rules is not None:
+            pairs = self._pairs_of(rules, nsoups)
+            birth, survive = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+            bptr, vptr = birth.ctypes.data, survive.ctypes.data
+        n = max(nsoups, 0)
+        out = np.zeros(n, dtype=SOUP_DTYPE)
+        cycle_start = np.zeros(n, dtype=np.int64)
+        ash_turn = np.zeros(n, dtype=np.int64)
+        nobj = np.zeros(n, dtype=np.int32)
+        obj = np.zeros((n, max(int(max_objects), 0)), dtype=OBJECT_DTYPE)
+        self._check(self._L.golhip_batch_search_objects(
+            self._h, nsoups, sptr, seed0, density_q32, max_turns, bptr, vptr, int(max_objects), int(reach),
+            out.ctypes.data, cycle_start.ctypes.data, ash_turn.ctypes.data, nobj.ctypes.data,
+            obj.ctypes.data if obj.size else None))
+        return SearchObjects(out, cycle_start, ash_turn, nobj, obj)
 
     @property
     def turn(self) -> int:

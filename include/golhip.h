@@ -422,7 +422,10 @@ int golhip_edge_wait(golhip_t h, double *total_ms, int64_t *blocks);
  *     allocates device memory: bytes, seeds, rules, counts, history and the census's results go
  *     through a transfer stage in chunks.  One more call allocates: the first
  *     golhip_batch_search_census (one chunk's ash boards, at most 64 MiB, and their turns, 512 KiB;
- *     the search buffers and the pattern table too if no earlier call has).
+ *     the search buffers and the pattern table too if no earlier call has).  And the objects calls
+ *     (golhip_batch_objects, golhip_batch_search_objects): the stage their results come back through
+ *     and pinned host memory of its size, each at most 64 MiB, and what golhip_batch_search_census
+ *     allocates for the search.
  *   - A batch has ONE turn counter.  Any golhip_batch_load_bytes, even of part of the batch, and any
  *     golhip_batch_init_random set it to 0 and clear every settle and period record: a batch is filled, then run.
  *   - golhip_batch_init_random: board i is bit for bit what golhip_init_random(seed_i, density_q32)
@@ -705,6 +708,112 @@ int golhip_batch_search_census(golhip_batch_t b, int64_t nsoups, const uint64_t 
                                uint32_t *counts  /* nsoups * npat, or NULL */,
                                uint32_t *residue /* nsoups, or NULL */,
                                uint8_t *ash_cells /* nsoups * height * width, or NULL */);
+/* The objects: every cluster of live cells of every board, found and hashed on the device.  The census
+ * counts the patterns of a list and says how many live cells the list does not explain; this call
+ * needs no list.  For every board it returns the clusters of live cells, each with a position, an
+ * extent, a population and a 64-bit shape hash that is the same for every translation, rotation and
+ * reflection of the shape: one tally over the hashes of a million boards names everything that
+ * occurred, listed or not.  One workgroup per board (gol_batch_objects) floods one cluster after the
+ * other in LDS.
+ *
+ * Cluster.
+ *   - reach is 1 or 2.
+ *   - Two live cells of a board are linked when their Chebyshev distance is at most reach.  On a torus
+ *     the distance is taken mod width and mod height.  On a plane it is taken in the rectangle.
+ *   - A cluster is a connected component of that relation.
+ *   - reach 1 gives 8-connected islands.
+ *   - reach 2 joins cells whose neighbourhoods share a cell.  Two clusters then cannot influence each
+ *     other in the next generation.  It keeps an aircraft carrier or a pulsar in one piece.
+ * Order.  The clusters of a board are numbered by their first cell in row-major order: smallest y,
+ * then smallest x.
+ * Extent, per axis.
+ *   - Take the cluster's occupancy along the axis: the columns, or rows, that hold one of its cells.
+ *   - On a plane, x0 is the smallest occupied column and w is the span to the largest.
+ *   - On a torus the occupancy is cyclic.  A connected cluster has at most one cyclic run of empty
+ *     columns of length >= reach.
+ *       - If that run exists, x0 is the column just after it, and w is the cyclic span from x0 to the
+ *         last occupied column.
+ *       - If it does not exist, the cluster winds round the torus on that axis: x0 = 0, w = width, and
+ *         flag WINDS_X is set.  A single cell on a torus of width <= reach winds by this rule.
+ *   - y0, h and WINDS_Y are defined the same way.
+ *   - A cell's place in the cluster is dx = (x - x0) mod width, dy = (y - y0) mod height.
+ * Hash.
+ *   - mix(v) is the splitmix64 finaliser on 64-bit unsigned values:
+ *       z = v + 0x9E3779B97F4A7C15
+ *       z = (z ^ z>>30) * 0xBF58476D1CE4E5B9
+ *       z = (z ^ z>>27) * 0x94D049BB133111EB
+ *       result z ^ z>>31
+ *   - The eight orientations k = 0..7 map (dx, dy) in a w x h box to (u, v) in an ow x oh box:
+ *       k   u        v        ow x oh
+ *       0   dx       dy       w x h
+ *       1   w-1-dx   dy       w x h
+ *       2   dx       h-1-dy   w x h
+ *       3   w-1-dx   h-1-dy   w x h
+ *       4   dy       dx       h x w
+ *       5   h-1-dy   dx       h x w
+ *       6   dy       w-1-dx   h x w
+ *       7   h-1-dy   w-1-dx   h x w
+ *   - H_k = (the sum over the cluster's cells of mix(v<<16 | u), mod 2^64) XOR mix(1<<32 | oh<<16 | ow).
+ *   - hash is the smallest H_k as an unsigned number.
+ *   - The sum does not depend on the order of the cells, so it can be reduced any way.
+ *   - A cluster that does not wind has the same hash wherever it lies and however it is turned.
+ *   - A winding cluster's hash depends on its position along the winding axis: its place is taken from
+ *     column (row) 0, so the same shape moved along that axis hashes differently.
+ * Record.  golhip_object_t is 32 bytes: int32 x, y, w, h; int32 population; uint32 flags; uint64 hash.
+ *   - Flag bit 0 is WINDS_X.  Bit 1 is WINDS_Y.
+ *   - Bit 2 is AT_BORDER.  It is set only on a plane, when a cell of the cluster is in row 0, row
+ *     height - 1, column 0 or column width - 1.  A glider dying at the edge has it.
+ *
+ * golhip_batch_objects(b, max_objects, reach, nobjects, objects):
+ *   - nobjects[i] is board i's total number of clusters, also when it exceeds max_objects.
+ *   - objects holds max_objects records per board.  The first min(nobjects[i], max_objects) records
+ *     of board i are written, at objects[i * max_objects ..], in the order above.  The rest are left
+ *     untouched.  objects may be NULL, for the counts alone.
+ *   - Bad arguments.  max_objects outside 1..4096, reach other than 1 or 2 and nobjects == NULL are
+ *     GOLHIP_ERR_ARG; the text names the argument, all checks come before any device work, and the
+ *     handle and outputs stay untouched.
+ *   - No side effects.  The call reads the boards as they are at the current turn.  It changes
+ *     nothing: boards, turn, rule(s), settle, period and search records, switches, topology and box
+ *     all stay as they were.  It is legal with tracking on or off and at any turn.  The rule plays no
+ *     part.
+ *   - Independence.  The result for board i depends on board i, the topology and reach only.  It does
+ *     not depend on nboards, on the board's position, on how boards are cut into launches, on
+ *     GOLHIP_STAGE_BYTES or on max_objects: the cap only cuts the list.
+ *   - Boards go out in launches of at most 65536 boards.  Counts and records come back in chunks
+ *     through the stage golhip_batch_search_census uses (at most 64 MiB, capped by GOLHIP_STAGE_BYTES
+ *     but never below one count and one record) and, the records, through pinned host memory of the
+ *     same size; a stage that does not hold a board's max_objects records takes the board's records
+ *     in several launches.  Both are allocated by the first call that needs them and freed by
+ *     golhip_batch_destroy. */
+#define GOLHIP_OBJECT_WINDS_X   1u
+#define GOLHIP_OBJECT_WINDS_Y   2u
+#define GOLHIP_OBJECT_AT_BORDER 4u
+typedef struct {
+    int32_t  x, y, w, h;   /* x0, y0 and the extent */
+    int32_t  population;
+    uint32_t flags;        /* GOLHIP_OBJECT_* */
+    uint64_t hash;
+} golhip_object_t;         /* 32 bytes */
+int golhip_batch_objects(golhip_batch_t b, int max_objects /* 1..4096 */, int reach /* 1 or 2 */,
+                         int32_t *nobjects /* nboards */,
+                         golhip_object_t *objects /* nboards * max_objects, or NULL */);
+/* The soup search with the objects of each soup's ash, no boards kept: golhip_batch_search_census with
+ * golhip_batch_objects in the census's place.  The same chunks, ash buffer and ash_turn; out,
+ * cycle_start and ash_turn are byte for byte golhip_batch_search_census's, and all three are required
+ * with nsoups > 0, as is nobjects.  nobjects[i] and objects[i * max_objects ..] are
+ * golhip_batch_objects's of the board board_i(ash_turn[i]) under the batch's topology: the recipe that
+ * reproduces it is golhip_batch_search_census's.  A soup without a repeat within max_turns has ash_turn
+ * -1 and nobjects 0.  Errors: golhip_batch_search's checks, then golhip_batch_objects's checks of
+ * max_objects and reach, in their words, all before any device work.  Side effects and independence
+ * are golhip_batch_search_census's: no output for soup i depends on nsoups, the soup's position, the
+ * chunking, GOLHIP_STAGE_BYTES or max_objects. */
+int golhip_batch_search_objects(golhip_batch_t b, int64_t nsoups, const uint64_t *seeds /* nsoups, or NULL */,
+                                uint64_t seed0, uint32_t density_q32, int64_t max_turns,
+                                const uint32_t *birth /* nsoups, or NULL */, const uint32_t *survive,
+                                int max_objects, int reach,
+                                golhip_soup_t *out /* nsoups */, int64_t *cycle_start /* nsoups */,
+                                int64_t *ash_turn /* nsoups */, int32_t *nobjects /* nsoups */,
+                                golhip_object_t *objects /* nsoups * max_objects, or NULL */);
 
 #ifdef __cplusplus
 }

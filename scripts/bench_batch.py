@@ -81,6 +81,16 @@ spread; (b) search_census beside search_exact; (c) the route it replaces, search
 + step(the largest stop_turn) + census on a batch of B boards (--route-calls times: a call steps every
 board to the slowest soup's turn).  Also the ash totals per object.
 
+--objects: the objects (Batch.objects, Batch.search_objects; gol_batch_objects) instead of the run above.
+--batches boards (4096 and 65536 by default) of 64 x 64, seeds 0 .. B - 1 at density 1/2, stepped 2000
+turns on the torus under B3/S23, reach 2, max_objects 64.  Before anything is timed nobjects and the
+records must equal np_objects (tests/objects_cases.py) on the first 256 boards.  Timed, host clock around
+whole calls: (a) the route it replaces, store() of every board, alone, and with np_objects' time on
+the 256-board sample scaled to B boards added; (b) one objects call, and the counts alone; (c) one
+census call with the 33 arrays of common_objects() on the same boards; (d) search_objects beside
+search_census on the same seeds (max_turns 16384, --max-turns).  Also the tally of the ashes: np.unique
+over the hashes, named where common_object_hashes() knows the hash.
+
 One JSON line on stdout; --out also writes it to a file.  There is no CPU fallback: without a GPU
 the script fails.
 """
@@ -485,6 +495,74 @@ def search_census_leg(a, res):
         print(json.dumps(row), file=sys.stderr, flush=True)
 
 
+def objects_leg(a, res):
+    """Batch.objects beside the route it replaces (store() and labelling on the host) and beside the
+    census, Batch.search_objects beside search_census, in this process."""
+    sys.path.insert(0, str(ROOT / "tests"))
+    import objects_cases
+
+    res["bench"] = "batch_objects"
+    res["turns"] = CENSUS_TURNS
+    res["reach"], res["max_objects"] = 2, 64
+    pats = [p for v in golhip.common_objects().values() for p in v]
+    known = golhip.common_object_hashes()
+    max_turns = a.max_turns or 16384
+    sample = 256
+    for B in ([int(v) for v in a.batches.split(",")] if a.batches else [4096, 65536]):
+        seeds = np.arange(B, dtype=np.uint64)
+        with golhip.Batch(64, 64, B) as b:
+            b.init_random(seeds=seeds)
+            b.step(CENSUS_TURNS)
+            nobj, obj = b.objects()
+            head = b.store(0, min(sample, B))
+            t0 = time.perf_counter()
+            want = objects_cases.np_objects(head, "torus", 2)
+            ref_s = time.perf_counter() - t0
+            wn, wo = objects_cases.table(want, 64)
+            assert np.array_equal(nobj[:len(head)], wn) and np.array_equal(obj[:len(head)], wo), B
+            assert np.array_equal(b.objects(max_objects=1)[0], nobj), B
+            out = np.empty((B, 64, 64), dtype=np.uint8)
+            store_med, store_min = median_s(lambda: b.store(out=out), 2, a.calls)
+            obj_med, obj_min = median_s(lambda: b.objects(), 2, a.calls)
+            lib, h = golhip.load_library(), b._h
+            cnt_med, cnt_min = median_s(lambda: lib.golhip_batch_objects(h, 64, 2, nobj.ctypes.data, None), 2, a.calls)
+            census_med, census_min = median_s(lambda: b.census(pats), 2, a.calls)
+            counts, _ = b.census(pats)
+        with golhip.Batch(64, 64, 1) as b:
+            so_med, so_min = median_s(lambda: b.search_objects(B, seeds=seeds, max_turns=max_turns), 2, a.calls)
+            sc_med, sc_min = median_s(lambda: b.search_census(B, pats, seeds=seeds, max_turns=max_turns), 2, a.calls)
+            so = b.search_objects(B, seeds=seeds, max_turns=max_turns)
+        tally = {}
+        for name, got_n, got_o in (("turn_2000", nobj, obj), ("search_ash", so.nobjects, so.objects)):
+            listed = got_o["hash"][np.arange(64)[None, :] < np.minimum(got_n, 64)[:, None]]
+            hashes, times = np.unique(listed, return_counts=True)
+            named = {}
+            for hsh, t in zip(hashes.tolist(), times.tolist()):
+                named[known.get(hsh, "other")] = named.get(known.get(hsh, "other"), 0) + t
+            top = sorted(zip(times.tolist(), hashes.tolist()), reverse=True)[:12]
+            tally[name] = {"clusters": int(got_n.sum()), "distinct_hashes": len(hashes), "named": named,
+                           "boards_over_the_cap": int((got_n > 64).sum()), "most_clusters": int(got_n.max()),
+                           "top": [[f"{hsh:016x}", t, known.get(hsh, "")] for t, hsh in top]}
+        host_s = store_med + ref_s * B / len(head)
+        row = {"width": 64, "height": 64, "boards": B, "tally": tally,
+               "census_match_totals": {k: int(sum(int(counts[:, i].sum()) for i, n in enumerate(
+                   [k2 for k2, v in golhip.common_objects().items() for _ in v]) if n == k)) for k in golhip.common_objects()},
+               "store_ms_median": round(store_med * 1e3, 3), "store_ms_min": round(store_min * 1e3, 3),
+               "reference_ms_per_board": round(ref_s / len(head) * 1e3, 3), "host_route_ms_scaled": round(host_s * 1e3, 1),
+               "objects_ms_median": round(obj_med * 1e3, 3), "objects_ms_min": round(obj_min * 1e3, 3),
+               "objects_counts_only_ms_median": round(cnt_med * 1e3, 3), "objects_counts_only_ms_min": round(cnt_min * 1e3, 3),
+               "census_ms_median": round(census_med * 1e3, 3), "census_ms_min": round(census_min * 1e3, 3),
+               "objects_boards_per_s": round(B / obj_med, 1), "store_over_objects": round(store_med / obj_med, 3),
+               "host_route_over_objects": round(host_s / obj_med, 1), "objects_over_census": round(obj_med / census_med, 3),
+               "max_turns": max_turns,
+               "search_objects_ms_median": round(so_med * 1e3, 3), "search_objects_ms_min": round(so_min * 1e3, 3),
+               "search_census_ms_median": round(sc_med * 1e3, 3), "search_census_ms_min": round(sc_min * 1e3, 3),
+               "search_objects_over_search_census": round(so_med / sc_med, 4)}
+        assert obj_med <= host_s, (obj_med, host_s)  # no slower than the route it replaces
+        res["shapes"].append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=7)
@@ -500,16 +578,29 @@ def main():
     ap.add_argument("--soups", type=int, default=4096, help="--search, --plane: soups per call, a multiple of 4096")
     ap.add_argument("--plane", action="store_true", help="the plane beside the torus (see above)")
     ap.add_argument("--box", help="--plane: the soup box, e.g. 16x16")
-    ap.add_argument("--max-turns", type=int, help="--plane, --exact: instead of the cases' max_turns")
+    ap.add_argument("--max-turns", type=int, help="--plane, --exact, --objects: instead of the cases' max_turns")
     ap.add_argument("--exact", action="store_true", help="search_exact beside search (see above)")
     ap.add_argument("--census", action="store_true", help="Batch.census beside store() + numpy (see above)")
     ap.add_argument("--search-census", action="store_true",
                     help="Batch.search_census beside search_exact and the route it replaces (see above)")
+    ap.add_argument("--objects", action="store_true",
+                    help="Batch.objects beside store() + numpy and the census, search_objects beside search_census")
     ap.add_argument("--parent-lib", type=Path, help="--search-census: a libgolhip.so built from the parent commit")
     ap.add_argument("--route-calls", type=int, default=3, help="--search-census: timed calls of the replaced route")
     a = ap.parse_args()
     assert a.calls >= 7
     assert a.rule or not a.per_board_rules, "--per-board-rules needs --rule"
+    if a.objects:
+        assert not (a.search_census or a.census or a.exact or a.plane or a.search or a.period or a.rule), \
+            "--objects replaces the other legs"
+        res = {"bench": "batch_objects", "version": golhip.load_library().golhip_version(), "calls": a.calls, "shapes": []}
+        objects_leg(a, res)
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            a.out.parent.mkdir(parents=True, exist_ok=True)
+            a.out.write_text(line + "\n")
+        return
     if a.search_census:
         assert not (a.census or a.exact or a.plane or a.search or a.period or a.rule), "--search-census replaces the other legs"
         res = {"bench": "batch_search_census", "version": golhip.load_library().golhip_version(), "calls": a.calls,
